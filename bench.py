@@ -16,9 +16,23 @@ exactly K steps and synchronize after them on every rank; the job's window runs 
 rank's start to the latest rank's end on the node's shared monotonic clock (both all-reduced), so
 barrier skew cannot shorten it; value = all boards x K / that window.
 
-Extra objects on the JSON line:
-  roofline      k_step_n is VALU-issue bound (boards in VGPRs, no memory traffic inside its step
-                loop): achieved = MODELLED VALU issue cycles per board-step (the shipped loop's
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline figure needs: set-up,
+warm-up, the K timed steps, the `--dump-outputs` files if asked for, and the JSON line (`roofline`
+below is arithmetic on the same timed region and the committed profiles: no run of its own).
+Everything else this file measures -- repeat_5, cpu_baseline, roofline.hbm, extras -- runs only
+with `--full`.
+
+`--dump-outputs DIR` writes what the last timed step left with the caller of `VecGame.step_n`
+(boards, reward, done and the drawn actions) as DIR/<name>.npy in float32 (rank 0's shard; a fixed
+seeded sample of the boards when the whole would pass 64 MB, the sampled board ids in rows.npy).
+With it the boards and step counters that the timed region starts from are put back to their
+values after the W warm-up steps just before the region, so the region's inputs do not depend on
+how many steps the time-based settle loop ran and two runs with the same arguments (or two builds
+of the library) can be compared output for output.
+
+Extra objects on the JSON line (`--full` unless noted):
+  roofline      (every run; its `hbm` entry only with `--full`) k_step_n is VALU-issue bound
+                (boards in VGPRs, no memory traffic inside its step loop): achieved = MODELLED VALU issue cycles per board-step (the shipped loop's
                 static instruction mix x measured per-instruction issue costs, plus the measured
                 operand costs -- literal, inline constant -- and the SIMD's SGPR-read limit,
                 tools/isa_hist.py model(); committed in profiles/<round>/pmc_k_step_n.json together
@@ -132,6 +146,10 @@ def _load_profile(name):
     return json.load(open(p)) if os.path.exists(p) else None
 
 
+UNTIMED_CALL_STEPS = 6000  # settle and dry-pass calls step at most this much (the default --steps): the untimed part
+                           # of a run does not grow with --steps
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: at most this much array data (under 64 MB with the .npy headers)
+DUMP_SEED = 0x48D0         # --dump-outputs: seed of the board sample
 SETTLE_S = 0.3   # minimum untimed stepping before a timed region: GPU clocks ramp over ~20 ms+
 SYNC_POLL = False  # --sync: poll the region's last HIP event before the closing synchronize
 SETTLE_SPIN = False  # --settle-spin: the settle loop polls its last event instead of sleeping in the wait
@@ -144,21 +162,23 @@ def _now():
     return time.clock_gettime_ns(time.CLOCK_MONOTONIC) * 1e-9
 
 
-def timed_steps(env, plan, W, chunk, world, dev):
+def timed_steps(env, plan, W, chunk, world, dev, pin_inputs=False):
     """W untimed warm-up steps through the same path (in calls of the timed chunk size) --
     continued, still untimed, until at least SETTLE_S of stepping has run -- then exactly sum(plan)
     steps. Opening: synchronize, barrier, synchronize, t0 (per rank); closing: synchronize, t1.
     -> (window seconds = max over ranks of t1 - min over ranks of t0 on the node's monotonic clock;
     device ms of the timed calls from HIP events on the launch stream, one entry per call;
-    start skew = max - min over ranks of t0)."""
+    start skew = max - min over ranks of t0). pin_inputs: the region starts from the boards and
+    counters as they were after the W warm-up steps, however long the settle loop stepped."""
     t_w = time.perf_counter()
     for c in chunks(W, chunk) if W else []:
         env.step_n(c, auto_reset=True)
     torch.cuda.synchronize(dev)
+    pinned = (env.boards.clone(), env.counters) if pin_inputs else None
     s = torch.cuda.current_stream(dev)
     done_ev = torch.cuda.Event()
     while time.perf_counter() - t_w < SETTLE_S:
-        env.step_n(chunk, auto_reset=True)
+        env.step_n(min(chunk, UNTIMED_CALL_STEPS), auto_reset=True)
         if SETTLE_SPIN:
             done_ev.record(s)
             while not done_ev.query():
@@ -172,9 +192,13 @@ def timed_steps(env, plan, W, chunk, world, dev):
     for _ in range(max(1, DRY_PASSES)):
         for (a, b), c in zip(ev, plan):
             a.record(s)
-            env.step_n(c, auto_reset=True)
+            env.step_n(min(c, UNTIMED_CALL_STEPS), auto_reset=True)
             b.record(s)
         ev[-1][1].synchronize()
+        torch.cuda.synchronize(dev)
+    if pinned is not None:
+        env.boards.copy_(pinned[0])
+        env.counters = pinned[1]
         torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
@@ -214,6 +238,24 @@ def timed_steps(env, plan, W, chunk, world, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         t0, t1, skew = -float(t[0]), float(t[1]), float(t[2]) + float(t[3])
     return t1 - t0, [a.elapsed_time(b) for a, b in ev], skew
+
+
+def dump_outputs(out_dir, env):
+    """--dump-outputs: what VecGame.step_n returned from the last timed step (boards, reward, done)
+    and the actions it drew, as float32 .npy files; all boards if that stays within DUMP_BYTES,
+    else a fixed seeded sample of them (ascending board ids, in rows.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    per_board = 4 * (16 + 3 + 1)                          # float32: board cells, reward, done, action, row id
+    rows = np.arange(env.n)
+    if env.n * per_board > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(env.n, DUMP_BYTES // per_board, replace=False))
+    idx = torch.from_numpy(rows).to(env.device)
+    arrays = {"boards": env.boards, "reward": env._zero_reward, "done": env.done, "actions": env.actions}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.index_select(0, idx).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float32 if env.n <= 1 << 24 else np.float64))
+    return {"dir": out_dir, "boards": int(rows.size), "of": env.n, "arrays": sorted(arrays) + ["rows"]}
 
 
 def single_step_hbm(dev, seed, n, launches):
@@ -519,9 +561,15 @@ def main():
     ap.add_argument("--boards", type=int, default=1 << 20, help="boards per GPU")
     ap.add_argument("--chunk", type=int, default=0, help="steps per r48_env_step_n call (0 = all K in one call)")
     ap.add_argument("--seed", type=int, default=0x20485EED)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: repeat_5, cpu_baseline, roofline.hbm "
+                         "and the extras (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32) and start the timed "
+                         "region from the state after the warm-up steps, so runs can be compared output for output")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: length of the cpu_baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip roofline.hbm and the extras")
     ap.add_argument("--settle", type=float, default=SETTLE_S,
                     help="seconds of untimed stepping before each timed region (after the warm-up steps)")
     ap.add_argument("--sync", choices=("poll", "block", "spin"), default="block",
@@ -551,7 +599,7 @@ def main():
         print("bench.py: --gpus %d but WORLD_SIZE=%d" % (args.gpus, world), file=sys.stderr)
         sys.exit(2)
     cpu_line = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_line = cpu_baseline(args.cpu_seconds)          # before this process touches the GPU
     # R48_DIST_BACKEND=gloo only rehearses several ranks sharing one GPU (RCCL refuses two ranks
     # on one device); the product path is RCCL ("nccl" on ROCm), one rank per GPU
@@ -575,7 +623,8 @@ def main():
     env.fill_random(7)                                    # SURVEY.md 8(d) synthetic start boards
     chunk = K if args.chunk <= 0 else max(1, min(args.chunk, K))
     plan = chunks(K, chunk)
-    elapsed, dev_ms, skew = timed_steps(env, plan, W, chunk, world, dev)
+    elapsed, dev_ms, skew = timed_steps(env, plan, W, chunk, world, dev, pin_inputs=args.dump_outputs is not None)
+    dumped = dump_outputs(args.dump_outputs, env) if args.dump_outputs is not None and rank == 0 else None
     value = world * n * K / elapsed
     line = {
         "metric": METRIC,
@@ -602,15 +651,17 @@ def main():
                    "visible_devices": ndev},
         "roofline": roofline_step_n(n, elapsed, sum(dev_ms), K),
     }
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     if cpu_line is not None:
         line["cpu_baseline"] = cpu_line
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # 5 repeats of the same K-step region, each re-warmed
         reps = [timed_steps(env, plan, chunk, chunk, world, dev)[0] for _ in range(5)]
         vals = [n * K / r for r in reps]
         line["repeat_5"] = {"values": vals, "median": sorted(vals)[2],
                             "spread": (max(vals) - min(vals)) / sorted(vals)[2], "sync": args.sync}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # the single-step HBM kernel: at 2^20 (cache-resident) and 2^26 boards (1 GiB, past the
         # 256 MiB Infinity Cache: the HBM-honest point)
         line["roofline"]["hbm"] = {"k_step_2p20": single_step_hbm(dev, args.seed, 1 << 20, 400),
@@ -636,7 +687,7 @@ def main():
         if not args.no_cpu_baseline:
             ex["cpu_strong_line"] = strong_cpu_line()
         line["extras"] = ex
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         # BASELINE configs[3] (A3C, 2^20 boards per GPU: 8M on 8 GPUs) and configs[4] (DQN,
         # 2^21 boards per GPU: 16M on 8 GPUs), every rank stepping its own shard, gradients
         # all-reduced over the process group's backend

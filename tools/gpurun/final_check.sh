@@ -10,4 +10,4 @@ R48_LIB=build/librein48_stamp.so timeout -k 10 120 python tools/exp_stamps.py 10
 && R48_LIB=build/librein48_stamp.so timeout -k 10 120 python tools/exp_stamps.py 1048576 1000 > $O/stamps_k1000.txt 2>&1 \
 && cat $O/stamps_k20.txt $O/stamps_k1000.txt \
 && bash tools/gpurun/check.sh $R noprof \
-&& echo "== 2-rank gloo rehearsal" && R48_DIST_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err && cat $O/bench_2rank_gloo.json
+&& echo "== 2-rank gloo rehearsal" && R48_DIST_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err && cat $O/bench_2rank_gloo.json

@@ -13,7 +13,7 @@ Writes under profiles/<round>/:
   pmc_k_step_2p20.json   k_step (one step per launch, boards through HBM), 2^20 boards
   pmc_k_step_2p26.json   same, 2^26 boards (past the 256 MiB Infinity Cache)
   kernel_stats_bench.csv rocprofv3 --kernel-trace --stats of `python3 bench.py --gpus 1 --steps 20
-                         --warmup 5` (the driver's command)
+                         --warmup 5 --full` (the driver's command with everything it measures)
   roofline_from_trace.json  the bench roofline recomputed from that trace (median k_step_n dispatch)
 usage: python tools/make_profiles.py <round> [gpurun_out/prof_<round>]"""
 import csv
@@ -115,7 +115,7 @@ def main():
                      "median dispatch time / (1024 SIMDs x 2.4 GHz); instr_rate_frac = SQ_INSTS_VALU per dispatch / median dispatch time / "
                      "(1024 SIMDs x 2.4 GHz / 2 cycles per full-rate wave64 instruction)",
           "trace": "profiles/%s/kernel_stats_bench.csv (rocprofv3 --kernel-trace --stats of python3 bench.py --gpus 1 "
-                   "--steps 20 --warmup 5)" % rnd}
+                   "--steps 20 --warmup 5 --full)" % rnd}
     json.dump(rt, open(os.path.join(OUT, "roofline_from_trace.json"), "w"), indent=1)
     print(json.dumps(rt, indent=1))
 

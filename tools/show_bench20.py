@@ -1,4 +1,4 @@
-"""Print value, repeat_5 values and the region's wall / device ms of bench.py JSON lines."""
+"""Print value, repeat_5 values and the region's wall / device ms of bench.py JSON lines (repeat_5 needs --full)."""
 import json
 import sys
 

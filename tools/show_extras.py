@@ -1,5 +1,5 @@
 """Print the headline value and the config-3/5 phase times of a bench.py JSON line.
-usage: python tools/show_extras.py bench.json"""
+usage: python tools/show_extras.py bench.json   (a `bench.py --full` line)"""
 import json
 import sys
 
