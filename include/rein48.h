@@ -564,6 +564,44 @@ int r48_bn_apply(const void *x, const void *residual, int64_t rows, int32_t C, c
 int r48_bn_backward_apply(const void *dy, const uint8_t *mask, const void *x, int64_t rows, int32_t C, const float *coef,
                           void *dx, void *stream);
 
+/* ---- Legal moves and afterstates (stateless: plain device pointers, so env boards and replay
+ * samples alike). Action codes 0 UP, 1 DOWN, 2 LEFT, 3 RIGHT. boards int8[n][16], 16-byte
+ * aligned. n == 0 is a no-op. An empty board has no legal move (and is not game over). ---- */
+/* bit a of legal[i] = action a changes board i (update_matrix's has_changed, GameClient.py:129-254) */
+int r48_boards_legal(const int8_t *boards, int64_t n, uint8_t *legal, void *stream);
+
+/* all four moves of every board in one launch (update_matrix, GameClient.py:129-254, once per
+ * action), ACTION-MAJOR so that each plane is itself a boards array any other entry point accepts
+ * and every store instruction is contiguous across the wave: after int8[4][n][16] (16-byte
+ * aligned; an illegal move's plane holds the unchanged board), reward int32[4][n] (nullable;
+ * merged tile values, 0 for an illegal move), legal uint8[n] (nullable) */
+int r48_boards_afterstates(const int8_t *boards, int64_t n, int8_t *after, int32_t *reward,
+                           uint8_t *legal, void *stream);
+
+/* r48_sample_actions (LocalAgent.choose_action, a3c.py:89-93) restricted to the legal moves of
+ * boards[i]: an illegal action's logit counts as -inf, and the draw never returns an illegal
+ * action (when rounding leaves the cumulative sum at or below u, the LAST LEGAL action is taken,
+ * not action 3). Same Philox contract, same logp / entropy outputs. A board with no legal move
+ * (game over, or empty) is treated as all-legal. */
+int r48_sample_actions_masked(const float *logits, const int8_t *boards, int64_t n, uint64_t seed,
+                              int64_t gid0, uint32_t ctr, int8_t *actions, float *logp, float *entropy,
+                              void *stream);
+
+/* r48_egreedy_actions restricted to legal moves (no reference code; Game.step's silent no-op on
+ * an unchanged move, GameClient.py:48-49, is what it avoids): same Philox words; u < eps -> the
+ * mulhi(w1, k)-th legal action in code order (k = number of legal moves; for k = 4 this is
+ * w1 >> 30, the unmasked rule), else the first argmax among the legal actions. No legal move: as
+ * r48_egreedy_actions. */
+int r48_egreedy_actions_masked(const float *q, const int8_t *boards, int64_t n, float eps, uint64_t seed,
+                               int64_t gid0, uint32_t ctr, int8_t *actions, void *stream);
+
+/* r48_td_target with a* and the bootstrap restricted to the legal moves of next_boards[i]
+ * (has_changed of update_matrix, GameClient.py:129-254); a next board with no legal move
+ * contributes 0 like done (it is terminal or empty). */
+int r48_td_target_masked(const float *reward, const uint8_t *done, const float *q_next_target,
+                         const float *q_next_online, const int8_t *next_boards, int64_t n, float gamma,
+                         int32_t log2_reward, float *y, void *stream);
+
 /* Thread-local message of the last failed call on this thread ("" if none). */
 const char *r48_last_error(void);
 /* "rein48 <version> gfx950" */

@@ -128,6 +128,11 @@ SIGNATURES = {
     "r48_mlp_train_grad_seg": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, C.c_float, _I32, _P, _P, _P, _P]),
     "r48_conv3x3_bn_in": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _FIN, _P]),
     "r48_bn_finish": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
+    "r48_boards_legal": (C.c_int, [_P, _I64, _P, _P]),
+    "r48_boards_afterstates": (C.c_int, [_P, _I64, _P, _P, _P, _P]),
+    "r48_sample_actions_masked": (C.c_int, [_P, _P, _I64, _U64, _I64, _U32, _P, _P, _P, _P]),
+    "r48_egreedy_actions_masked": (C.c_int, [_P, _P, _I64, C.c_float, _U64, _I64, _U32, _P, _P]),
+    "r48_td_target_masked": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_float, _I32, _P, _P]),
     "r48_last_error": (C.c_char_p, []),
     "r48_version": (C.c_char_p, []),
 }

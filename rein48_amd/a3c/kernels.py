@@ -34,15 +34,32 @@ def board_features(boards, exponents=False, dtype=torch.float32, out=None):
     return out
 
 
-def sample_actions(logits, seed, ctr, gid0=0, want_logp=False, want_entropy=False):
-    """choose_action (a3c.py:89-93) for every row of logits [n, 4] (post-ReLU, pre-softmax)."""
+def _rows_boards(boards, n, like):
+    """boards int8 [n, 16] on `like`'s device, for a masked kernel over n rows."""
+    _dev(boards, "boards", torch.int8)
+    if boards.device != like.device:
+        raise ValueError("boards must be on %s, got %s" % (like.device, boards.device))
+    if boards.numel() != 16 * n:
+        raise ValueError("boards must hold %d boards of 16 cells, got %d cells" % (n, boards.numel()))
+    return boards
+
+
+def sample_actions(logits, seed, ctr, gid0=0, want_logp=False, want_entropy=False, boards=None):
+    """choose_action (a3c.py:89-93) for every row of logits [n, 4] (post-ReLU, pre-softmax). With
+    boards int8 [n, 16] the draw is restricted to each board's legal moves (r48_sample_actions_masked)."""
     _dev(logits, "logits", torch.float32)
     n = logits.numel() // 4
+    if boards is not None:
+        _rows_boards(boards, n, logits)
     act = torch.empty(n, dtype=torch.int8, device=logits.device)
     logp = torch.empty(n, dtype=torch.float32, device=logits.device) if want_logp else None
     ent = torch.empty(n, dtype=torch.float32, device=logits.device) if want_entropy else None
-    check(_lib.load().r48_sample_actions(ptr(logits), n, int(seed) & (2 ** 64 - 1), int(gid0), int(ctr) & 0xFFFFFFFF,
-                                         ptr(act), ptr(logp), ptr(ent), _stream(logits)))
+    tail = (n, int(seed) & (2 ** 64 - 1), int(gid0), int(ctr) & 0xFFFFFFFF, ptr(act), ptr(logp), ptr(ent),
+            _stream(logits))
+    if boards is None:
+        check(_lib.load().r48_sample_actions(ptr(logits), *tail))
+    else:
+        check(_lib.load().r48_sample_actions_masked(ptr(logits), ptr(boards), *tail))
     return act, logp, ent
 
 

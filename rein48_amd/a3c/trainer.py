@@ -377,26 +377,35 @@ class A3CTrainer:
         self.rollout()
         return self.update()
 
-    def policy(self, seed=0x5A3C):
+    def policy(self, seed=0x5A3C, mask_illegal=False):
         """The current policy as `policy(boards int8 [n, 16], t) -> actions int8 [n]` (choose_action,
         a3c.py:89-93: a draw from the softmax; Philox keyed by (seed, board, t)) for
-        evaluate.play_episodes. Weights are packed once, at the call."""
+        evaluate.play_episodes. Weights are packed once, at the call. mask_illegal: the draw is
+        restricted to each board's legal moves (the forward returns logits, then
+        r48_sample_actions_masked); training and the rollout kernels are not masked."""
         cfg = self.cfg
         exps = cfg.features == "exponents"
         if cfg.net == "cnn" and cfg.bf16 and cfg.fused_policy:
             wfrag, bias = pack_cnn(self.net)
+            if mask_illegal:
+                return lambda boards, t: K.sample_actions(
+                    cnn_forward(boards, wfrag, bias, exponents=exps, logits=True, value=False)[0], seed, t,
+                    boards=boards)[0]
             return lambda boards, t: cnn_forward(boards, wfrag, bias, exponents=exps, logits=False, value=False,
                                                  actions=True, seed=seed, ctr=t)[2]
         if self._mlp_fused():
             from .fused import mlp_forward, pack_mlp
             w = pack_mlp(self.net)
+            if mask_illegal:
+                return lambda boards, t: K.sample_actions(
+                    mlp_forward(boards, w, exponents=exps, logits=True, value=False)[0], seed, t, boards=boards)[0]
             return lambda boards, t: mlp_forward(boards, w, exponents=exps, logits=False, value=False, actions=True,
                                                  seed=seed, ctr=t)[2]
 
         def act(boards, t):
             with torch.no_grad():
                 logits, _ = self._net(self._features(boards))
-            return K.sample_actions(logits.float().contiguous(), seed, t)[0]
+            return K.sample_actions(logits.float().contiguous(), seed, t, boards=boards if mask_illegal else None)[0]
         return act
 
     def scores(self):

@@ -21,7 +21,8 @@ assumed, with a warning). It refuses (ValueError) a file whose resume could not 
 another draw contract (R48_DRAW_CONTRACT: the same counters would give other draws), another rank's
 shard (its first global board id, which keys every Philox draw), or a configuration that differs in a
 field that fixes buffer shapes, the draws (seed), the network's inputs (features) or numerics (bf16),
-or the loss (mode). Hyper-parameters such as lr, gamma or epsilon may differ (a deliberate change).
+the loss (mode), or which actions are taken and bootstrapped (the DQN's mask_illegal). Hyper-parameters
+such as lr, gamma or epsilon may differ (a deliberate change).
 """
 import dataclasses
 import warnings
@@ -35,7 +36,8 @@ FORMAT = 2
 # configuration fields a checkpoint must agree on: buffer shapes, draws, inputs, numerics, loss
 _MATCH_FIELDS = {
     "a3c": ("n_boards", "max_steps", "net", "seed", "mode", "features", "bf16"),
-    "dqn": ("n_boards", "replay_capacity", "channels", "blocks", "bn", "bf16", "seed", "reward_transform"),
+    "dqn": ("n_boards", "replay_capacity", "channels", "blocks", "bn", "bf16", "seed", "reward_transform",
+            "mask_illegal"),
 }
 
 
@@ -141,9 +143,12 @@ def load(trainer, path):
         raise ValueError("checkpoint: %s holds the shard starting at board %d, this trainer's starts at %d "
                          "(another rank's file?)" % (path, st["gid0"], _gid0(trainer, kind)))
     cfg = dataclasses.asdict(trainer.cfg)
+    # a field the file's configuration predates (mask_illegal) had its default when the file was written
+    defaults = {f.name: f.default for f in dataclasses.fields(trainer.cfg)}
     for f in _MATCH_FIELDS[kind]:
-        if cfg[f] != st["cfg"][f]:
-            raise ValueError("checkpoint: %s = %r in the trainer, %r in %s" % (f, cfg[f], st["cfg"][f], path))
+        theirs = st["cfg"].get(f, defaults[f])
+        if cfg[f] != theirs:
+            raise ValueError("checkpoint: %s = %r in the trainer, %r in %s" % (f, cfg[f], theirs, path))
     dev = trainer.device
     with torch.no_grad():
         trainer.net.load_state_dict(st["net"])   # copies into the flat buffers' views

@@ -18,6 +18,7 @@
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
+#include "r48_select.h"
 
 namespace r48 {
 void set_last_error(const std::string &msg);
@@ -26,7 +27,6 @@ void set_last_error(const std::string &msg);
 namespace {
 
 constexpr int kBlock = 256;
-constexpr uint32_t kSampleTag = 0xA3Cu;
 
 inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
@@ -77,7 +77,8 @@ __global__ __launch_bounds__(kBlock) void k_features_bf16(const int8_t *__restri
     o[1] = make_uint4(packed[4], packed[5], packed[6], packed[7]);
 }
 
-// softmax over 4 logits + inverse-CDF draw with a Philox uniform (24-bit, [0,1))
+// softmax over 4 logits + inverse-CDF draw with a Philox uniform (r48_select.h sample_row, shared with
+// the legal-move masked form in r48_moves.hip)
 __global__ __launch_bounds__(kBlock) void k_sample(const float *__restrict__ logits, int64_t n, int64_t gid0,
                                                    uint32_t k0, uint32_t k1, uint32_t ctr,
                                                    int8_t *__restrict__ actions, float *__restrict__ logp,
@@ -86,25 +87,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(const float *__restrict__ log
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
         return;
-    const float4 z = *reinterpret_cast<const float4 *>(logits + 4 * i);
-    const float m = fmaxf(fmaxf(z.x, z.y), fmaxf(z.z, z.w));
-    const float e0 = __expf(z.x - m), e1 = __expf(z.y - m), e2 = __expf(z.z - m), e3 = __expf(z.w - m);
-    const float s = e0 + e1 + e2 + e3, inv = 1.0f / s;
-    const float p0 = e0 * inv, p1 = e1 * inv, p2 = e2 * inv, p3 = e3 * inv;
-    uint32_t w[4] = {(uint32_t)(gid0 + i), (uint32_t)((uint64_t)(gid0 + i) >> 32), ctr, kSampleTag};
-    r48::philox4x32_10(w, k0, k1);
-    const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
-    // first k with cdf(k) > u (np.random.choice's searchsorted(..., side='right'))
-    const float c0 = p0, c1 = c0 + p1, c2 = c1 + p2;
-    const int a = (c0 > u) ? 0 : (c1 > u) ? 1 : (c2 > u) ? 2 : 3;
-    actions[i] = (int8_t)a;
-    if (logp) {
-        const float za = a == 0 ? z.x : a == 1 ? z.y : a == 2 ? z.z : z.w;
-        logp[i] = za - m - __logf(s);
-    }
-    if (entropy)
-        entropy[i] = -(p0 * __logf(p0 + 1e-5f) + p1 * __logf(p1 + 1e-5f) + p2 * __logf(p2 + 1e-5f) +
-                       p3 * __logf(p3 + 1e-5f));
+    r48::sample_row<false>(logits, i, 15u, gid0, k0, k1, ctr, actions, logp, entropy);
 }
 
 // targets[t][i] for t < len[i]; 0 for t >= len[i]. DROP_LAST: the reference's scan

@@ -299,6 +299,97 @@ R48_HD bool game_over(const Board &r, uint32_t n_blank)
     return n_blank == 0u && eq == 0u;
 }
 
+// Which of the four moves would change the board (update_matrix's has_changed,
+// GameClient.py:129-254): bit a (0 UP, 1 DOWN, 2 LEFT, 3 RIGHT). A closed form, not four moves: a
+// move toward a wall changes the board iff some adjacent pair along that axis is (empty, tile)
+// in the move's direction -- a tile can slide -- or is two equal tiles -- a merge; equal tiles
+// with only empties between them already have an (empty, tile) pair. The equal-pair term is
+// shared by the two directions of an axis. Vertical pairs compare row word r with row word
+// r + 1; horizontal pairs compare a row word with itself shifted down one byte (byte c against
+// cell c + 1; byte 3 meets the zero shifted in). Flags live in bit 7 of each byte (bytes <=
+// 0x7F); the other bits are don't-care until the final & 0x80808080. An empty board has no
+// legal move (and is not game over: has_game_over needs a full board).
+R48_HD uint32_t legal_mask(const Board &r)
+{
+    constexpr uint32_t K7 = 0x7F7F7F7Fu, K8 = 0x80808080u;
+    // bit 7: the cell holds a tile
+    const uint32_t n0 = r.w0 + K7, n1 = r.w1 + K7, n2 = r.w2 + K7, n3 = r.w3 + K7;
+    // vertical: bit 7 of K8 - (a ^ b) = the two cells are equal
+    uint32_t ev = (K8 - (r.w0 ^ r.w1)) & n1;
+    ev = bitop3<0xF8u>(ev, K8 - (r.w1 ^ r.w2), n2);      // ev | (eq & tile)
+    ev = bitop3<0xF8u>(ev, K8 - (r.w2 ^ r.w3), n3);
+    uint32_t up = n1 & ~n0;                              // (empty above, tile below) slides up
+    up = bitop3<0xF2u>(up, n1, n2);                      // up | (~n1 & n2)
+    up = bitop3<0xF2u>(up, n2, n3);
+    uint32_t dn = n0 & ~n1;                              // (tile above, empty below) slides down
+    dn = bitop3<0xF4u>(dn, n1, n2);                      // dn | (n1 & ~n2)
+    dn = bitop3<0xF4u>(dn, n2, n3);
+    // horizontal: s = the right-hand neighbour of every cell (0 for column 3), m = it is a tile
+    const uint32_t s0 = r.w0 >> 8, s1 = r.w1 >> 8, s2 = r.w2 >> 8, s3 = r.w3 >> 8;
+    const uint32_t m0 = s0 + K7, m1 = s1 + K7, m2 = s2 + K7, m3 = s3 + K7;
+    uint32_t eh = (K8 - (r.w0 ^ s0)) & m0;
+    eh = bitop3<0xF8u>(eh, K8 - (r.w1 ^ s1), m1);
+    eh = bitop3<0xF8u>(eh, K8 - (r.w2 ^ s2), m2);
+    eh = bitop3<0xF8u>(eh, K8 - (r.w3 ^ s3), m3);
+    uint32_t lf = m0 & ~n0;                              // (empty, tile) slides left
+    lf = bitop3<0xF2u>(lf, n1, m1);
+    lf = bitop3<0xF2u>(lf, n2, m2);
+    lf = bitop3<0xF2u>(lf, n3, m3);
+    uint32_t rt = n0 & ~m0;                              // (tile, empty) slides right; column 3 has no
+    rt = bitop3<0xF4u>(rt, n1, m1);                      // neighbour: masked out below
+    rt = bitop3<0xF4u>(rt, n2, m2);
+    rt = bitop3<0xF4u>(rt, n3, m3);
+    const uint32_t fu = bitop3<0xA8u>(ev, up, K8), fd = bitop3<0xA8u>(ev, dn, K8);   // (a | b) & c
+    const uint32_t fl = bitop3<0xA8u>(eh, lf, K8), fr = bitop3<0xA8u>(eh, rt, 0x00808080u);
+    return (fu ? 1u : 0u) | (fd ? 2u : 0u) | (fl ? 4u : 0u) | (fr ? 8u : 0u);
+}
+
+// update_matrix (GameClient.py:129-254) with the action a compile-time parameter: the
+// orientation selects of to_lines / from_lines fold away (UP: nothing, DOWN: word order, LEFT /
+// RIGHT: one transpose each way). The move half of step_board: an unchanged move returns the
+// input board (from_lines inverts to_lines exactly) and reward 0 (no merge, nothing to sum).
+template <int A, bool REWARD>
+R48_HD uint32_t move_rows(const Board &rows, Board &out)
+{
+    static_assert(A >= 0 && A < 4, "action code 0..3");
+    Board L = to_lines(rows, (uint32_t)A);
+    const uint32_t reward = move_lines<REWARD>(L);
+    out = from_lines(L, (uint32_t)A);
+    return reward;
+}
+
+// All four moves of one board. The orientation work is done once: one transpose of the input
+// serves LEFT and RIGHT, row order serves UP and DOWN (3 transposes in all instead of the 8 of
+// four to_lines / from_lines round trips).
+struct Moves4 {
+    Board up, down, left, right;
+    uint32_t r_up, r_down, r_left, r_right;   // merge rewards (0 unless REWARD)
+};
+
+template <bool REWARD>
+R48_HD Moves4 move_rows4(const Board &r)
+{
+    Moves4 m;
+    const Board t = transpose(r);
+    m.up = r;
+    m.r_up = move_lines<REWARD>(m.up);
+    Board d{r.w3, r.w2, r.w1, r.w0};
+    m.r_down = move_lines<REWARD>(d);
+    m.down = Board{d.w3, d.w2, d.w1, d.w0};
+    Board l = t;
+    m.r_left = move_lines<REWARD>(l);
+    m.left = transpose(l);
+    Board g{t.w3, t.w2, t.w1, t.w0};
+    m.r_right = move_lines<REWARD>(g);
+    m.right = transpose(Board{g.w3, g.w2, g.w1, g.w0});
+    return m;
+}
+
+R48_HD bool differs(const Board &a, const Board &b)
+{
+    return (or3(a.w0 ^ b.w0, a.w1 ^ b.w1, a.w2 ^ b.w2) | (a.w3 ^ b.w3)) != 0u;
+}
+
 R48_HD uint32_t row_sum(uint32_t w)
 {
     uint32_t s = 0;

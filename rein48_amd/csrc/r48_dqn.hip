@@ -19,6 +19,7 @@
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
+#include "r48_select.h"
 
 namespace r48 {
 void set_last_error(const std::string &msg);
@@ -27,7 +28,6 @@ void set_last_error(const std::string &msg);
 namespace {
 
 constexpr int kBlock = 256;
-constexpr uint32_t kEgreedyTag = 0xD0Eu;
 constexpr int kPlanes = 18;
 
 inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
@@ -63,21 +63,9 @@ __global__ __launch_bounds__(kBlock) void k_onehot(const int8_t *__restrict__ bo
         o[k] = (T)(e == (uint32_t)k ? 1.0f : 0.0f);
 }
 
-__device__ __forceinline__ uint32_t argmax4(float4 q)
-{
-    uint32_t a = 0;
-    float m = q.x;
-    if (q.y > m) { m = q.y; a = 1; }
-    if (q.z > m) { m = q.z; a = 2; }
-    if (q.w > m) { a = 3; }
-    return a;
-}
+using r48::pick;
 
-__device__ __forceinline__ float pick(float4 q, uint32_t a)
-{
-    return a == 0 ? q.x : a == 1 ? q.y : a == 2 ? q.z : q.w;
-}
-
+// r48_select.h egreedy_row / td_row, shared with the legal-move masked forms in r48_moves.hip
 __global__ __launch_bounds__(kBlock) void k_egreedy(const float *__restrict__ q, int64_t n, float eps, uint32_t k0,
                                                     uint32_t k1, int64_t gid0, uint32_t ctr,
                                                     int8_t *__restrict__ actions)
@@ -85,12 +73,7 @@ __global__ __launch_bounds__(kBlock) void k_egreedy(const float *__restrict__ q,
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
         return;
-    const uint64_t gid = (uint64_t)(gid0 + i);
-    uint32_t w[4] = {(uint32_t)gid, (uint32_t)(gid >> 32), ctr, kEgreedyTag};
-    r48::philox4x32_10(w, k0, k1);
-    const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
-    const float4 qv = reinterpret_cast<const float4 *>(q)[i];
-    actions[i] = (int8_t)(u < eps ? (w[1] >> 30) : argmax4(qv));
+    r48::egreedy_row<false>(q, i, 15u, eps, k0, k1, gid0, ctr, actions);
 }
 
 template <bool DOUBLE, bool LOG2>
@@ -103,11 +86,7 @@ __global__ __launch_bounds__(kBlock) void k_td_target(const float *__restrict__ 
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
         return;
-    const float4 qt = reinterpret_cast<const float4 *>(q_next_target)[i];
-    const uint32_t a = DOUBLE ? argmax4(reinterpret_cast<const float4 *>(q_next_online)[i]) : argmax4(qt);
-    const float boot = (done && done[i]) ? 0.0f : pick(qt, a);
-    const float r = LOG2 ? log2f(1.0f + reward[i]) : reward[i];   // trainer.py _reward, torch.log2(1.0 + r)
-    y[i] = r + gamma * boot;
+    r48::td_row<DOUBLE, LOG2, false>(reward, done, q_next_target, q_next_online, i, 15u, false, gamma, y);
 }
 
 // ---- Huber loss of Q(s)[a] against the TD target and its gradient (DQNLearner.learn):

@@ -58,6 +58,7 @@ class DQNConfig:
     act_chunk: int = 1 << 18         # boards per Q forward while acting (PyTorch path)
     fused: bool = True               # eval-mode Q through r48_resnet_q_forward (bf16, C=64, 4 blocks)
     fused_step: bool = True          # training step through train_step.ResNetTrainStep (bf16 GPU, C=64)
+    mask_illegal: bool = False       # act, and bootstrap the TD target, over legal moves only (r48_moves.hip)
     seed: int = 0
 
 
@@ -218,6 +219,12 @@ class DQNTrainer(DQNLearner):
     @torch.no_grad()
     def act(self):
         eps, gid0 = self.epsilon(), self.rank * self.cfg.n_boards
+        if self.cfg.mask_illegal:
+            # Q as usual (one fused forward, or the PyTorch net), then the epsilon-greedy draw over the
+            # legal moves of the env's boards (their legal set is computed in the kernel's registers)
+            q = self._q_masked(self.env.boards, out=self.q)
+            return egreedy_actions(q, eps, self.cfg.seed, self.steps, gid0=gid0, out=self.actions,
+                                   boards=self.env.boards)
         if self.use_fused:
             from .fused import resnet_q_forward
             _, a = resnet_q_forward(self.env.boards, self.packed(self.net), q=False, actions=True, eps=eps,
@@ -227,12 +234,27 @@ class DQNTrainer(DQNLearner):
         self.q_values(self.net, self.env.boards, out=self.q)
         return egreedy_actions(self.q, eps, self.cfg.seed, self.steps, gid0=gid0, out=self.actions)
 
-    def policy(self, eps=0.01, seed=0x5D09):
+    def _q_masked(self, boards, out=None):
+        """The online net's eval-mode Q for the masked selection: one r48_resnet_q_forward with q
+        requested on the fused path (a fresh tensor; `out` is not needed), q_values on the PyTorch path."""
+        if self.use_fused:
+            from .fused import resnet_q_forward
+            return resnet_q_forward(boards.contiguous(), self.packed(self.net))[0]
+        return self.q_values(self.net, boards, out=out)
+
+    def policy(self, eps=0.01, seed=0x5D09, mask_illegal=None):
         """The online net's epsilon-greedy policy as `policy(boards, t) -> actions` (Philox keyed by
         (seed, board, t); a small eps keeps a greedy policy from repeating a move that changes
-        nothing) for evaluate.play_episodes."""
+        nothing) for evaluate.play_episodes. mask_illegal (default: the config's setting) restricts
+        the draw and the argmax to each board's legal moves: every step then changes the board, so
+        eps=0.0 cannot stall."""
+        masked = self.cfg.mask_illegal if mask_illegal is None else bool(mask_illegal)
+
         def act(boards, t):
             with torch.no_grad():
+                if masked:
+                    boards = boards.contiguous()
+                    return egreedy_actions(self._q_masked(boards), eps, seed, t, boards=boards)
                 if self.use_fused:
                     from .fused import resnet_q_forward
                     return resnet_q_forward(boards.contiguous(), self.packed(self.net), q=False, actions=True,
@@ -270,8 +292,10 @@ class DQNTrainer(DQNLearner):
             qt = self.q_eval(self.target, b["next_state"]).contiguous()
             qo = self.q_eval(self.net, b["next_state"]).contiguous() if c.double else None
             rw = b["reward"].contiguous()
-            y = td_target(rw, b["done"], qt, qo, c.gamma, log2_reward=True) if c.reward_transform == "log2" \
-                else td_target(self._reward(rw), b["done"], qt, qo, c.gamma)
+            nb = b["next_state"].contiguous() if c.mask_illegal else None   # a* over the legal moves of s'
+            y = td_target(rw, b["done"], qt, qo, c.gamma, log2_reward=True, next_boards=nb) \
+                if c.reward_transform == "log2" else td_target(self._reward(rw), b["done"], qt, qo, c.gamma,
+                                                               next_boards=nb)
         out = self.learn(x, b["action"], y, sync=sync)
         out["batch"] = b
         return out

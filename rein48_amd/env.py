@@ -219,6 +219,18 @@ class VecGame:
         check(self._lib.r48_env_score(self._env, ptr(out), self._s()))
         return out
 
+    def legal_actions(self, out=None):
+        """uint8[N]: bit a set iff action a would change board i (moves.legal_actions)."""
+        from .moves import legal_actions
+        return legal_actions(self.boards, out=out)
+
+    def afterstates(self, after=None, reward=None, legal=None, want_reward=True, want_legal=True):
+        """All four moves of every board, action-major (moves.afterstates): (after int8[4, N, 16],
+        reward int32[4, N] or None, legal uint8[N] or None). The env's boards are not changed."""
+        from .moves import afterstates
+        return afterstates(self.boards, after=after, reward=reward, legal=legal, want_reward=want_reward,
+                           want_legal=want_legal)
+
     def values(self):
         """Boards as raw tile values int32[N,4,4] (the reference's state_matrix encoding)."""
         e = self.boards.to(torch.int32)

@@ -25,6 +25,35 @@ def random_policy(seed=0):
     return policy
 
 
+def afterstate_policy(value=None):
+    """One-ply afterstate policy: among the legal actions, the one maximising reward[a] +
+    value(after[a]), ties to the lowest action code; a board with no legal move gets action 0.
+    `value` maps int8 boards [m, 16] to float [m]; None is the greedy-merge baseline (the legal move
+    with the largest merge reward), a yardstick that needs no network. The expansion is one
+    r48_boards_afterstates launch; the selection over [4, n] is plain torch."""
+    from .moves import afterstates
+    bits = {}
+
+    def policy(boards, t):
+        boards = boards.contiguous()
+        after, reward, legal = afterstates(boards)
+        n = legal.shape[0]
+        score = reward.to(torch.float32)
+        if value is not None:
+            score = score + value(after.view(4 * n, 16)).to(torch.float32).view(4, n)
+        b = bits.get(boards.device)
+        if b is None:
+            b = bits[boards.device] = torch.tensor([[1], [2], [4], [8]], dtype=torch.uint8, device=boards.device)
+        ok = (legal.unsqueeze(0) & b) != 0
+        score = torch.where(ok, score, torch.full_like(score, -float("inf")))
+        best = score.max(dim=0, keepdim=True).values
+        # lowest action code among the legal maximisers; 4 = none (no legal move) -> action 0
+        code = torch.arange(4, dtype=torch.int8, device=boards.device).view(4, 1).expand(4, n)
+        first = torch.where((score == best) & ok, code, torch.full_like(code, 4)).min(dim=0).values
+        return torch.where(first == 4, torch.zeros_like(first), first)
+    return policy
+
+
 @torch.no_grad()
 def play_episodes(policy, n_boards, device="cuda:0", seed=0, max_steps=20_000, check_every=50):
     """Play n_boards episodes to game over (or max_steps). Returns a dict: mean / max score (tile
