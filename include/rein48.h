@@ -602,6 +602,44 @@ int r48_td_target_masked(const float *reward, const uint8_t *done, const float *
                          const float *q_next_online, const int8_t *next_boards, int64_t n, float gamma,
                          int32_t log2_reward, float *y, void *stream);
 
+/* ---- N-tuple network on afterstates (r48_ntuple.hip; stateless like the entry points above).
+ * A layout is m tuples (1..8) of L distinct cells each (2..6): cells uint8[m][L] ON THE HOST, cell
+ * numbers 0..15 row-major as the board bytes are. tables float[m][16^L], contiguous. For tuple t
+ * on board b the entry index is sum_k min(b[cell_k], 15) << 4k (exponents above 15 share entry
+ * 15), and
+ *     V(b) = sum over t and over the 8 symmetries g of the square of tables[t][index(g . b, t)],
+ * every (t, g) counted, duplicates included; fp32, one fixed order shared by every entry point, so
+ * r48_ntuple_value and r48_ntuple_act agree bit for bit. R48_EINVAL (before any HIP call) for NULL
+ * or misaligned boards, n < 0, m or L out of range, a cell >= 16 or a cell repeated within a tuple.
+ * n == 0 is a no-op. ---- */
+int r48_ntuple_value(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                     const float *tables, float *value, void *stream);
+
+/* One-ply afterstate search in one kernel: the four moves are made in registers, V is evaluated
+ * for the legal ones only, action = argmax over legal a of (float)reward[a] + V(after[a]), ties to
+ * the lowest code. The outputs describe the chosen move: actions int8[n], after int8[n][16]
+ * (nullable; 16-byte aligned), value float[n] = V(after) (nullable), reward int32[n] (nullable;
+ * merged tile values), legal uint8[n] (nullable; the board's whole legal set as r48_boards_legal).
+ * A board with no legal move: action 0, after = the board, value 0, reward 0, legal 0. */
+int r48_ntuple_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                   const float *tables, int8_t *actions, int8_t *after, float *value, int32_t *reward,
+                   uint8_t *legal, void *stream);
+
+/* The TD update in two launches, both over the hits (i, t, g) of the boards with valid[i] != 0
+ * (valid NULL: all). Scratch: acc int64[m][16^L], cnt uint32[m][16^L], which MUST BE ALL ZERO ON
+ * ENTRY to r48_ntuple_accumulate (r48_ntuple_apply leaves them zero again).
+ *   accumulate: cnt[e] += 1, acc[e] += llrintf(clamp(delta[i], +-2^20) * 65536) -- integer
+ *               atomics, so the sums do not depend on the order of the hits
+ *   apply:      every entry hit moves ONCE by step * (acc[e] * 2^-16 / cnt[e]), the mean delta of
+ *               its hits (the lane whose exchange takes the count takes the sum too); acc and cnt
+ *               of every entry hit are zero afterwards. Pass the boards and valid of accumulate.
+ * No float atomics: the tables after apply are bitwise reproducible. */
+int r48_ntuple_accumulate(const int8_t *boards, int64_t n, const float *delta, const uint8_t *valid,
+                          const uint8_t *cells, int32_t m, int32_t L, int64_t *acc, uint32_t *cnt,
+                          void *stream);
+int r48_ntuple_apply(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
+                     int32_t L, float step, float *tables, int64_t *acc, uint32_t *cnt, void *stream);
+
 /* Thread-local message of the last failed call on this thread ("" if none). */
 const char *r48_last_error(void);
 /* "rein48 <version> gfx950" */

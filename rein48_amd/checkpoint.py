@@ -9,6 +9,9 @@ is bit-identical to training that never stopped (tests/test_checkpoint_gpu.py):
               Adam's m, v and step, the env's boards and counters, the env-step count, the update
               count, and the HBM replay ring (its counters and, unless replay=False, its contents in
               slot order: 38 B per stored transition)
+  NTupleTrainer  the tables, the env's boards and counters, the previous step's afterstates, values,
+              done and valid flags, and the step count (the update is deterministic: integer
+              atomics, one plain table update per entry)
 Draws are keyed by counters, not by RNG state in memory, so restoring the
 counters restores every later draw.
 
@@ -38,6 +41,7 @@ _MATCH_FIELDS = {
     "a3c": ("n_boards", "max_steps", "net", "seed", "mode", "features", "bf16"),
     "dqn": ("n_boards", "replay_capacity", "channels", "blocks", "bn", "bf16", "seed", "reward_transform",
             "mask_illegal"),
+    "ntuple": ("n_boards", "seed"),     # and the layout's cells, compared as cells (a name or a list in cfg)
 }
 
 
@@ -46,14 +50,21 @@ def _gid0(trainer, kind):
     return int(trainer.gid0) if kind == "a3c" else int(trainer.rank) * int(trainer.cfg.n_boards)
 
 
+def _cells(net):
+    return [list(t) for t in net.cells]
+
+
 def _kind(trainer):
     from .a3c.trainer import A3CTrainer
     from .dqn.trainer import DQNLearner
+    from .ntuple import NTupleTrainer
+    if isinstance(trainer, NTupleTrainer):
+        return "ntuple"
     if isinstance(trainer, A3CTrainer):
         return "a3c"
     if isinstance(trainer, DQNLearner):
         return "dqn"
-    raise TypeError("checkpoint: expected an A3CTrainer or a DQNLearner / DQNTrainer, got %r" % type(trainer))
+    raise TypeError("checkpoint: expected an A3CTrainer, a DQNLearner / DQNTrainer or an NTupleTrainer, got %r" % type(trainer))
 
 
 def _cpu(t):
@@ -109,7 +120,12 @@ def save(trainer, path, replay=True):
         torch.cuda.synchronize(trainer.device)
     st = {"format": FORMAT, "kind": kind, "cfg": dataclasses.asdict(trainer.cfg), "updates": int(trainer.updates),
           "draw_contract": DRAW_CONTRACT, "gid0": _gid0(trainer, kind)}
-    if kind == "a3c":
+    if kind == "ntuple":
+        cfg = dict(st["cfg"], layout=_cells(trainer.net))     # a layout given as tuples is saved as lists
+        st.update(cfg=cfg, cells=_cells(trainer.net), tables=_cpu(trainer.net.tables), env=_env_state(trainer.env),
+                  prev_after=_cpu(trainer.prev_after), prev_value=_cpu(trainer.prev_value),
+                  prev_done=_cpu(trainer.prev_done), prev_valid=_cpu(trainer.prev_valid))
+    elif kind == "a3c":
         st.update(net=_cpu_state(trainer.net), ms=_cpu(trainer.opt.ms), mom=_cpu(trainer.opt.mom),
                   env=_env_state(trainer.env), sample_ctr=int(trainer.sample_ctr))
     else:
@@ -149,10 +165,17 @@ def load(trainer, path):
         theirs = st["cfg"].get(f, defaults[f])
         if cfg[f] != theirs:
             raise ValueError("checkpoint: %s = %r in the trainer, %r in %s" % (f, cfg[f], theirs, path))
+    if kind == "ntuple" and st["cells"] != _cells(trainer.net):
+        raise ValueError("checkpoint: layout cells %r in the trainer, %r in %s" % (_cells(trainer.net), st["cells"], path))
     dev = trainer.device
     with torch.no_grad():
-        trainer.net.load_state_dict(st["net"])   # copies into the flat buffers' views
-        if kind == "a3c":
+        if kind == "ntuple":
+            trainer.net.tables.copy_(st["tables"].to(dev))
+            _load_env(trainer.env, st["env"])
+            for k in ("prev_after", "prev_value", "prev_done", "prev_valid"):
+                getattr(trainer, k).copy_(st[k].to(dev))
+        elif kind == "a3c":
+            trainer.net.load_state_dict(st["net"])   # copies into the flat buffers' views
             trainer.opt.ms.copy_(st["ms"].to(dev))
             trainer.opt.mom.copy_(st["mom"].to(dev))
             _load_env(trainer.env, st["env"])
@@ -161,6 +184,7 @@ def load(trainer, path):
             trainer._wepoch += 1                 # repack the kernels' weight images
             trainer._mask = None
         else:
+            trainer.net.load_state_dict(st["net"])
             trainer.target.load_state_dict(st["target"])
             trainer.opt.m.copy_(st["adam_m"].to(dev))
             trainer.opt.v.copy_(st["adam_v"].to(dev))

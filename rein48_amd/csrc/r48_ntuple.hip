@@ -1,0 +1,246 @@
+// r48_ntuple.hip -- the n-tuple network (r48_ntuple.h) behind include/rein48.h: value, the fused
+// one-ply afterstate search, and the two halves of the per-entry-mean TD update. Stateless like
+// r48_moves.hip: plain device pointers plus the layout's cells on the host.
+//
+//   k_nt_value       board -> V(board): 8m table gathers, fp32 sum in the header's fixed order
+//   k_nt_act         board -> the four moves in registers (move_rows4), V of the legal ones only,
+//                    argmax of reward + V with ties to the lowest code; writes the chosen move's
+//                    afterstate / V / reward and the legal set. No afterstate plane goes through
+//                    HBM on the way to the values.
+//   k_nt_accumulate  every hit (i, t, g) of a valid board: cnt[e] += 1, acc[e] += delta_i in
+//                    fixed point (2^-16) -- integer atomics, so the sums do not depend on order
+//   k_nt_apply       every hit again: the one lane whose exchange takes the entry's count also
+//                    takes its sum and moves tables[e] by step * mean delta, once; both scratch
+//                    words are zero afterwards. No float atomics: bitwise reproducible.
+// One board per lane, one 16-byte board load; templated on the tuple length L so the cell loops
+// unroll; the expanded layout travels by value in the kernel arguments (wave-uniform).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "../../include/rein48.h"
+#include "r48_board.h"
+#include "r48_ntuple.h"
+#include "r48_select.h"
+
+namespace r48 {
+void set_last_error(const std::string &msg);
+}
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr float kDeltaClamp = 1048576.0f;   // 2^20
+constexpr float kFixedOne = 65536.0f;       // acc counts delta in units of 2^-16
+
+inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
+
+int fail(int code, const std::string &msg)
+{
+    r48::set_last_error(msg);
+    return code;
+}
+
+int launched(const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        r48::set_last_error(std::string(what) + ": " + hipGetErrorString(e));
+        return R48_EHIP;
+    }
+    return R48_OK;
+}
+
+bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_value(const int8_t *__restrict__ boards, int64_t n,
+                                                     const r48::NtLayout lay, const float *__restrict__ tables,
+                                                     float *__restrict__ value)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    value[i] = r48::nt_value<L>(r48::nt_pack(r48::load_board(boards, i)), lay, tables);
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_act(const int8_t *__restrict__ boards, int64_t n,
+                                                   const r48::NtLayout lay, const float *__restrict__ tables,
+                                                   int8_t *__restrict__ actions, int8_t *__restrict__ after,
+                                                   float *__restrict__ value, int32_t *__restrict__ reward,
+                                                   uint8_t *__restrict__ legal)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    const r48::Board b = r48::load_board(boards, i);
+    const r48::Moves4 m = r48::move_rows4<true>(b);
+    const uint32_t lg = (r48::differs(m.up, b) ? 1u : 0u) | (r48::differs(m.down, b) ? 2u : 0u) |
+                        (r48::differs(m.left, b) ? 4u : 0u) | (r48::differs(m.right, b) ? 8u : 0u);
+    // no legal move: action 0, the board itself, value 0, reward 0
+    r48::Board best_b = b;
+    float best_s = 0.0f, best_v = 0.0f;
+    uint32_t best_r = 0u, best_a = 0u;
+    bool have = false;
+#pragma unroll 1
+    for (uint32_t a = 0; a < 4u; a++) {
+        if (!((lg >> a) & 1u))
+            continue;
+        // a is uniform: scalar-conditioned selects, no indexed private array
+        const r48::Board c = a == 0u ? m.up : a == 1u ? m.down : a == 2u ? m.left : m.right;
+        const uint32_t r = a == 0u ? m.r_up : a == 1u ? m.r_down : a == 2u ? m.r_left : m.r_right;
+        const float v = r48::nt_value<L>(r48::nt_pack(c), lay, tables);
+        const float s = (float)(int32_t)r + v;
+        if (!have || s > best_s) {
+            have = true;
+            best_s = s;
+            best_v = v;
+            best_r = r;
+            best_a = a;
+            best_b = c;
+        }
+    }
+    actions[i] = (int8_t)best_a;
+    if (after)
+        *reinterpret_cast<uint4 *>(after + 16 * i) = make_uint4(best_b.w0, best_b.w1, best_b.w2, best_b.w3);
+    if (value)
+        value[i] = best_v;
+    if (reward)
+        reward[i] = (int32_t)best_r;
+    if (legal)
+        legal[i] = (uint8_t)lg;
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_accumulate(const int8_t *__restrict__ boards, int64_t n,
+                                                          const float *__restrict__ delta,
+                                                          const uint8_t *__restrict__ valid, const r48::NtLayout lay,
+                                                          unsigned long long *__restrict__ acc,
+                                                          uint32_t *__restrict__ cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || (valid && !valid[i]))
+        return;
+    const r48::NtBoard b = r48::nt_pack(r48::load_board(boards, i));
+    const float d = fminf(fmaxf(delta[i], -kDeltaClamp), kDeltaClamp);
+    const unsigned long long q = (unsigned long long)llrintf(d * kFixedOne);   // two's complement: wraps as int64 adds
+    for (int t = 0; t < lay.m; t++) {
+#pragma unroll
+        for (int g = 0; g < r48::kNtSyms; g++) {
+            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g);
+            atomicAdd(&cnt[e], 1u);
+            atomicAdd(&acc[e], q);
+        }
+    }
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_apply(const int8_t *__restrict__ boards, int64_t n,
+                                                     const uint8_t *__restrict__ valid, const r48::NtLayout lay,
+                                                     float step, float *__restrict__ tables,
+                                                     unsigned long long *__restrict__ acc, uint32_t *__restrict__ cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || (valid && !valid[i]))
+        return;
+    const r48::NtBoard b = r48::nt_pack(r48::load_board(boards, i));
+    for (int t = 0; t < lay.m; t++) {
+#pragma unroll
+        for (int g = 0; g < r48::kNtSyms; g++) {
+            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g);
+            const uint32_t c = atomicExch(&cnt[e], 0u);
+            if (c != 0u) {
+                // the only lane of this launch that sees a count for e: it owns tables[e]
+                const long long a = (long long)atomicExch(&acc[e], 0ull);
+                tables[e] += step * (((float)a * (1.0f / kFixedOne)) / (float)c);
+            }
+        }
+    }
+}
+
+// the arguments every entry point shares: boards, n, the layout
+int check_common(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                 r48::NtLayout &lay)
+{
+    if (!boards || !aligned(boards, 16) || n < 0)
+        return fail(R48_EINVAL, std::string(fn) + ": boards NULL or not 16-byte aligned, or n < 0");
+    if (const char *why = r48::nt_expand(cells, m, L, lay))
+        return fail(R48_EINVAL, std::string(fn) + ": bad layout: " + why);
+    return R48_OK;
+}
+
+#define R48_NT_DISPATCH(KERNEL, ...)                                                                       \
+    switch (lay.L) {                                                                                       \
+    case 2: hipLaunchKernelGGL(KERNEL<2>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+    case 3: hipLaunchKernelGGL(KERNEL<3>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+    case 4: hipLaunchKernelGGL(KERNEL<4>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+    case 5: hipLaunchKernelGGL(KERNEL<5>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+    default: hipLaunchKernelGGL(KERNEL<6>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+    }
+
+}  // namespace
+
+extern "C" {
+
+int r48_ntuple_value(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                     float *value, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_common("r48_ntuple_value", boards, n, cells, m, L, lay))
+        return rc;
+    if (!tables || !value || !aligned(tables, 4) || !aligned(value, 4))
+        return fail(R48_EINVAL, "r48_ntuple_value: tables/value NULL or not 4-byte aligned");
+    if (n == 0)
+        return R48_OK;
+    R48_NT_DISPATCH(k_nt_value, boards, n, lay, tables, value)
+    return launched("k_nt_value");
+}
+
+int r48_ntuple_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                   int8_t *actions, int8_t *after, float *value, int32_t *reward, uint8_t *legal, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_common("r48_ntuple_act", boards, n, cells, m, L, lay))
+        return rc;
+    if (!tables || !actions || !aligned(tables, 4) || !aligned(after, 16) || !aligned(value, 4) || !aligned(reward, 4))
+        return fail(R48_EINVAL, "r48_ntuple_act: tables/actions NULL, after not 16-byte aligned, or tables / value / "
+                                "reward not 4-byte aligned");
+    if (n == 0)
+        return R48_OK;
+    R48_NT_DISPATCH(k_nt_act, boards, n, lay, tables, actions, after, value, reward, legal)
+    return launched("k_nt_act");
+}
+
+int r48_ntuple_accumulate(const int8_t *boards, int64_t n, const float *delta, const uint8_t *valid,
+                          const uint8_t *cells, int32_t m, int32_t L, int64_t *acc, uint32_t *cnt, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_common("r48_ntuple_accumulate", boards, n, cells, m, L, lay))
+        return rc;
+    if (!delta || !acc || !cnt || !aligned(delta, 4) || !aligned(acc, 8) || !aligned(cnt, 4))
+        return fail(R48_EINVAL, "r48_ntuple_accumulate: delta/acc/cnt NULL, acc not 8-byte aligned, or delta / cnt "
+                                "not 4-byte aligned");
+    if (n == 0)
+        return R48_OK;
+    R48_NT_DISPATCH(k_nt_accumulate, boards, n, delta, valid, lay, reinterpret_cast<unsigned long long *>(acc), cnt)
+    return launched("k_nt_accumulate");
+}
+
+int r48_ntuple_apply(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m, int32_t L,
+                     float step, float *tables, int64_t *acc, uint32_t *cnt, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_common("r48_ntuple_apply", boards, n, cells, m, L, lay))
+        return rc;
+    if (!tables || !acc || !cnt || !aligned(tables, 4) || !aligned(acc, 8) || !aligned(cnt, 4))
+        return fail(R48_EINVAL, "r48_ntuple_apply: tables/acc/cnt NULL, acc not 8-byte aligned, or tables / cnt not "
+                                "4-byte aligned");
+    if (n == 0)
+        return R48_OK;
+    R48_NT_DISPATCH(k_nt_apply, boards, n, valid, lay, step, tables, reinterpret_cast<unsigned long long *>(acc), cnt)
+    return launched("k_nt_apply");
+}
+
+}  // extern "C"

@@ -55,10 +55,11 @@ def afterstate_policy(value=None):
 
 
 @torch.no_grad()
-def play_episodes(policy, n_boards, device="cuda:0", seed=0, max_steps=20_000, check_every=50):
+def play_episodes(policy, n_boards, device="cuda:0", seed=0, max_steps=20_000, check_every=50, return_scores=False):
     """Play n_boards episodes to game over (or max_steps). Returns a dict: mean / max score (tile
     sum), mean episode length, the fraction that finished, and the distribution of the largest
-    tile (exponent -> fraction of boards)."""
+    tile (exponent -> fraction of boards); with return_scores also "scores", every board's score
+    (float64 [n_boards] on the host)."""
     env = VecGame(n_boards, device=device, seed=seed)
     env.reset()
     length = torch.zeros(n_boards, dtype=torch.int32, device=env.boards.device)
@@ -74,6 +75,9 @@ def play_episodes(policy, n_boards, device="cuda:0", seed=0, max_steps=20_000, c
     score = env.score().double()
     top = env.boards.max(dim=1).values.long()
     hist = torch.bincount(top, minlength=18).double() / n_boards
-    return {"boards": n_boards, "mean_score": float(score.mean()), "max_score": float(score.max()),
+    out = {"boards": n_boards, "mean_score": float(score.mean()), "max_score": float(score.max()),
             "mean_length": float(length.double().mean()), "finished": float((~alive).double().mean()),
             "steps_run": t, "max_tile_exponent_hist": {int(e): float(f) for e, f in enumerate(hist) if f > 0}}
+    if return_scores:
+        out["scores"] = score.cpu()
+    return out

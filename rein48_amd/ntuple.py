@@ -1,0 +1,188 @@
+"""N-tuple network on afterstates, trained by TD(0) (rein48_amd/csrc/r48_ntuple.hip).
+
+The value of a board is a sum of lookup-table entries over `m` board patterns (tuples of `L`
+cells) and their 8 symmetries: V(b) = sum_t sum_g tables[t][index(g . b, t)], index = sum_k
+min(b[cell_k], 15) << 4k (DESIGN.md "N-tuple network"). It fills the `value` of
+evaluate.afterstate_policy, fused: NTupleNet.act makes the four moves, evaluates the legal
+afterstates and picks the best in one kernel.
+
+The reference has no such learner (its value-based code is the unfinished DDPG); the method is the
+TD-afterstate n-tuple network of Szubert & Jaskowski (CIG 2014) with its per-entry step
+normalisation taken over the batch: every table entry moves by alpha / (8m) times the MEAN delta of
+the boards that hit it, so one board alone moves V(s') by alpha * delta and 64 copies of it move it
+by the same amount.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import torch
+
+from . import _lib
+from ._lib import check, ptr
+from .a3c.kernels import _dev, _stream
+from .env import VecGame
+from .moves import _boards, _out
+
+LAYOUTS = {
+    "4x6": ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10)),
+    "lines-squares": ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 4, 5), (1, 2, 5, 6), (5, 6, 9, 10)),
+}
+
+
+def layout_cells(layout):
+    """A layout name or a sequence of equal-length cell tuples -> tuple of tuples of ints."""
+    cells = LAYOUTS[layout] if isinstance(layout, str) else layout
+    cells = tuple(tuple(int(c) for c in t) for t in cells)
+    if not 1 <= len(cells) <= 8:
+        raise ValueError("a layout has 1..8 tuples, got %d" % len(cells))
+    L = len(cells[0])
+    if not 2 <= L <= 6 or any(len(t) != L for t in cells):
+        raise ValueError("the tuples of a layout have one length, 2..6 cells")
+    for t in cells:
+        if any(not 0 <= c < 16 for c in t) or len(set(t)) != L:
+            raise ValueError("tuple %r: cells are distinct numbers 0..15" % (t,))
+    return cells
+
+
+class NTupleNet:
+    """The tables float32 [m, 16^L] and the update's scratch (acc int64, cnt uint32 held as int32,
+    same shape; zero between calls) on one GPU."""
+
+    def __init__(self, layout="4x6", device="cuda:0"):
+        self.cells = layout_cells(layout)
+        self.m, self.L = len(self.cells), len(self.cells[0])
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("NTupleNet device must be a GPU, got %s" % self.device)
+        flat = [c for t in self.cells for c in t]
+        self._cells = (C.c_uint8 * len(flat))(*flat)
+        size = 16 ** self.L
+        self.tables = torch.zeros((self.m, size), dtype=torch.float32, device=self.device)
+        self.acc = torch.zeros((self.m, size), dtype=torch.int64, device=self.device)
+        self.cnt = torch.zeros((self.m, size), dtype=torch.int32, device=self.device)
+        self._lib = _lib.load()
+
+    def _lay(self):
+        return self._cells, self.m, self.L
+
+    def value(self, boards, out=None):
+        """float32 [n]: V of int8 boards [..., 16]."""
+        n = _boards(boards)
+        out = _out(out, "out", torch.float32, (n,), boards)
+        check(self._lib.r48_ntuple_value(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(out), _stream(boards)))
+        return out
+
+    def act(self, boards, actions=None, after=None, value=None, reward=None, legal=None):
+        """The one-ply afterstate search -> (actions int8 [n], after int8 [n, 16], value float32 [n],
+        reward int32 [n], legal uint8 [n]) of the chosen move: argmax over the legal moves of
+        reward + V(afterstate), ties to the lowest code. No legal move: action 0, the board itself,
+        value 0, reward 0, legal 0."""
+        n = _boards(boards)
+        actions = _out(actions, "actions", torch.int8, (n,), boards)
+        after = _out(after, "after", torch.int8, (n, 16), boards)
+        value = _out(value, "value", torch.float32, (n,), boards)
+        reward = _out(reward, "reward", torch.int32, (n,), boards)
+        legal = _out(legal, "legal", torch.uint8, (n,), boards)
+        check(self._lib.r48_ntuple_act(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(actions), ptr(after),
+                                       ptr(value), ptr(reward), ptr(legal), _stream(boards)))
+        return actions, after, value, reward, legal
+
+    def accumulate(self, boards, delta, valid=None):
+        """First half of td_update: per-entry hit counts and fixed-point delta sums into the scratch."""
+        n = _boards(boards)
+        _dev(delta, "delta", torch.float32)
+        if delta.numel() != n or (valid is not None and _dev(valid, "valid", torch.uint8).numel() != n):
+            raise ValueError("delta / valid must have one element per board (%d)" % n)
+        check(self._lib.r48_ntuple_accumulate(ptr(boards), n, ptr(delta), ptr(valid), *self._lay(), ptr(self.acc),
+                                              ptr(self.cnt), _stream(boards)))
+
+    def apply(self, boards, step, valid=None):
+        """Second half: every entry the boards hit moves by step * its mean delta; scratch back to zero."""
+        n = _boards(boards)
+        if valid is not None and _dev(valid, "valid", torch.uint8).numel() != n:
+            raise ValueError("valid must have one element per board (%d)" % n)
+        check(self._lib.r48_ntuple_apply(ptr(boards), n, ptr(valid), *self._lay(), float(step), ptr(self.tables),
+                                         ptr(self.acc), ptr(self.cnt), _stream(boards)))
+
+    def td_update(self, afterstates, delta, alpha, valid=None):
+        """tables[e] += alpha / (8m) * mean over the valid boards hitting e of delta, for every entry
+        hit. Deterministic: integer atomics, then one plain update per entry."""
+        self.accumulate(afterstates, delta, valid)
+        self.apply(afterstates, alpha / (8.0 * self.m), valid)
+
+    def policy(self):
+        """`policy(boards, t) -> actions` for evaluate.play_episodes: the fused greedy search."""
+        def policy(boards, t):
+            return self.act(boards.contiguous())[0]
+        return policy
+
+    def state_dict(self):
+        return {"cells": [list(t) for t in self.cells], "tables": self.tables.detach().to("cpu", copy=True)}
+
+    def load_state_dict(self, st):
+        if [list(t) for t in self.cells] != [list(t) for t in st["cells"]]:
+            raise ValueError("NTupleNet: the layout is %r, the saved one %r" % (self.cells, st["cells"]))
+        self.tables.copy_(st["tables"].to(self.device))
+
+    def save(self, path):
+        torch.save(self.state_dict(), path)
+
+    def load(self, path):
+        self.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+
+
+@dataclass
+class NTupleConfig:
+    n_boards: int = 4096
+    layout: object = "4x6"           # a name in LAYOUTS or a sequence of cell tuples
+    alpha: float = 0.25
+    seed: int = 0
+
+
+class NTupleTrainer:
+    """Board-synchronous TD(0) on afterstates, one env step of every board per train_step():
+      1. act on the env boards: a_t, the afterstate s'_t, v_t = V(s'_t), the merge reward r_t
+      2. boards with a previous afterstate: target = 0 if the previous step ended the episode, else
+         r_t + v_t; delta = target - v_{t-1}, where v_{t-1} is the value act returned one step ago
+         (one batch update old); td_update(s'_{t-1}, delta, alpha, valid)
+      3. env.step(a_t, auto_reset=True); s'_t, v_t, done become the "previous"
+    No exploration: the spawns randomise. Single GPU (an all-reduce of the table updates is not
+    built)."""
+
+    def __init__(self, cfg: NTupleConfig, device="cuda:0"):
+        self.cfg = cfg
+        self.device = torch.device(device)
+        self.rank = 0
+        n = cfg.n_boards
+        self.net = NTupleNet(cfg.layout, self.device)
+        self.env = VecGame(n, device=self.device, seed=cfg.seed)
+        self.device = self.env.device
+        self.env.reset()
+        d = self.device
+        self.actions = torch.zeros(n, dtype=torch.int8, device=d)
+        self.reward = torch.zeros(n, dtype=torch.int32, device=d)
+        self.legal = torch.zeros(n, dtype=torch.uint8, device=d)
+        # this step's outputs and the previous step's, swapped every step
+        self.after, self.prev_after = (torch.zeros((n, 16), dtype=torch.int8, device=d) for _ in range(2))
+        self.value, self.prev_value = (torch.zeros(n, dtype=torch.float32, device=d) for _ in range(2))
+        self.prev_done = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.prev_valid = torch.zeros(n, dtype=torch.uint8, device=d)   # the first step has no previous afterstate
+        self.delta = torch.zeros(n, dtype=torch.float32, device=d)
+        self.updates = 0
+
+    @torch.no_grad()
+    def train_step(self):
+        net, env = self.net, self.env
+        net.act(env.boards, self.actions, self.after, self.value, self.reward, self.legal)
+        target = torch.where(self.prev_done != 0, torch.zeros_like(self.value), self.reward.float() + self.value)
+        torch.sub(target, self.prev_value, out=self.delta)
+        net.td_update(self.prev_after, self.delta, self.cfg.alpha, self.prev_valid)
+        _, _, done = env.step(self.actions, auto_reset=True)
+        self.after, self.prev_after = self.prev_after, self.after
+        self.value, self.prev_value = self.prev_value, self.value
+        self.prev_done.copy_(done)
+        self.prev_valid.copy_(self.legal != 0)   # an afterstate exists where a move did
+        self.updates += 1
+
+    def policy(self):
+        return self.net.policy()
