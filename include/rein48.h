@@ -625,6 +625,24 @@ int r48_ntuple_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_
                    const float *tables, int8_t *actions, int8_t *after, float *value, int32_t *reward,
                    uint8_t *legal, void *stream);
 
+/* Expectimax search over the afterstate values, depth 1 or 2, one kernel, one board per wave. For
+ * a move a that changes the board (afterstate s_a, merge reward r_a):
+ *   depth 1: Q(a) = (float)r_a + V(s_a), r48_ntuple_act's score;
+ *   depth 2: Q(a) = (float)r_a + S_a / (float)(10 |E|), E the empty cells of s_a,
+ *            S_a = sum over c in E of (9 leaf(s_a[c <- 1]) + leaf(s_a[c <- 2])), leaf(child) =
+ *            r48_ntuple_act's best score on the child, 0 where the child has no legal move
+ *            (the spawn rule: uniform over the blanks, P(4) = 0.1).
+ * Illegal moves have Q = -inf. Outputs: actions int8[n] = the first maximiser of Q (lowest code;
+ * 0 where no move is legal), q float[n][4] (nullable), legal uint8[n] (nullable; as
+ * r48_boards_legal). fp32; S_a adds the sixteen cells' terms (+0 for a cell that holds a tile) in
+ * one fixed tree order that depends on the cell numbers alone, so q is bitwise reproducible and
+ * does not depend on the board's place in the batch (r48_ntuple.h states the order). R48_EINVAL
+ * as above, and for depth not 1 or 2, NULL tables or actions, tables or q not 4-byte aligned,
+ * or n beyond 4 * (2^31 - 1) boards (the grid). */
+int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                      const float *tables, int32_t depth, int8_t *actions, float *q, uint8_t *legal,
+                      void *stream);
+
 /* The TD update in two launches, both over the hits (i, t, g) of the boards with valid[i] != 0
  * (valid NULL: all). Scratch: acc int64[m][16^L], cnt uint32[m][16^L], which MUST BE ALL ZERO ON
  * ENTRY to r48_ntuple_accumulate (r48_ntuple_apply leaves them zero again).

@@ -16,6 +16,26 @@
 //
 // Summation order (the contract every kernel here shares, so value and act agree bit for bit):
 // fp32, starting from 0, hits in the order p = 8t + g = 0, 1, ..., 8m - 1.
+//
+// The search (k_nt_search, and nt_search_board for one board on the host). For a move a that
+// changes the board: afterstate s_a, merge reward r_a, and
+//     depth 1   Q(a) = (float)r_a + V(s_a)                                  (act's score)
+//     depth 2   Q(a) = (float)r_a + S_a / (float)(10 |E|),  E = the empty cells of s_a,
+//               S_a = sum over c in E of (9 leaf(s_a[c <- 1]) + leaf(s_a[c <- 2])),
+//               leaf(child) = max over the child's legal moves a' of (float)r_a' + V(after_a'), and
+//               0 where the child has no legal move (the game-over value of the trainer's target)
+// -- the spawn rule of r48_board.h: uniform over the blanks, P(4) = 0.1. Illegal moves have
+// Q = -inf; the action is the first maximiser of Q (lowest code), 0 where no move is legal.
+// Arithmetic (the contract the kernel and the host share, so they agree bit for bit):
+//   - fp32 throughout, V is nt_value
+//   - a cell's term is fmaf(9, leaf(c, 1), leaf(c, 2)): one rounding, none with integer tables,
+//     where S_a is then exact (below 2^24) and symmetric boards tie bit for bit; one division
+//     by 10 |E| afterwards
+//   - S_a adds the 16 terms x_0 .. x_15 of the cells in row-major order, x_c = +0 where cell c
+//     of s_a holds a tile, as the xor butterfly does: x_c += x_(c ^ 1), then ^ 2, ^ 4, ^ 8, i.e.
+//     (((x0 + x1) + (x2 + x3)) + ((x4 + x5) + (x6 + x7))) + (the same of x8 .. x15). fp32 addition
+//     commutes, so every lane of the butterfly holds these bits. The order depends on nothing
+//     but the cell numbers: not on the batch, on n, or on which cells are empty.
 #pragma once
 #include <stdint.h>
 
@@ -149,6 +169,181 @@ R48_HD float nt_value(const NtBoard &b, const NtLayout &lay, const float *__rest
             sum += v[j];
     }
     return sum;
+}
+
+// ---- the search -------------------------------------------------------------------------------
+
+#if defined(__HIPCC__)
+#define R48_NO_UNROLL _Pragma("unroll 1")
+#else
+#define R48_NO_UNROLL
+#endif
+
+R48_HD float nt_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// bit a: move a changes the board
+R48_HD uint32_t nt_legal4(const Moves4 &m, const Board &b)
+{
+    return (differs(m.up, b) ? 1u : 0u) | (differs(m.down, b) ? 2u : 0u) | (differs(m.left, b) ? 4u : 0u) |
+           (differs(m.right, b) ? 8u : 0u);
+}
+
+// move a of the four, by selects (no indexed private array)
+R48_HD Board nt_pick(const Moves4 &m, uint32_t a)
+{
+    // word by word: a select between whole structs becomes a select of addresses, and with a
+    // per-lane a the moves then live in private memory
+    const bool v = a < 2u, o = (a & 1u) != 0u;
+    return Board{sel(v, sel(o, m.down.w0, m.up.w0), sel(o, m.right.w0, m.left.w0)),
+                 sel(v, sel(o, m.down.w1, m.up.w1), sel(o, m.right.w1, m.left.w1)),
+                 sel(v, sel(o, m.down.w2, m.up.w2), sel(o, m.right.w2, m.left.w2)),
+                 sel(v, sel(o, m.down.w3, m.up.w3), sel(o, m.right.w3, m.left.w3))};
+}
+
+R48_HD uint32_t nt_pick_reward(const Moves4 &m, uint32_t a)
+{
+    return sel(a < 2u, sel((a & 1u) != 0u, m.r_down, m.r_up), sel((a & 1u) != 0u, m.r_right, m.r_left));
+}
+
+// the exponent in cell c (0..15)
+R48_HD uint32_t nt_cell(const Board &b, uint32_t c)
+{
+    const uint32_t w = sel((c & 8u) != 0u, sel((c & 4u) != 0u, b.w3, b.w2), sel((c & 4u) != 0u, b.w1, b.w0));
+    return (w >> (8u * (c & 3u))) & 0xFFu;
+}
+
+// (float)reward + V(afterstate): the score of one move, at either depth
+template <int L>
+R48_HD float nt_score(const Board &after, uint32_t reward, const NtLayout &lay, const float *__restrict__ tables)
+{
+    return (float)(int32_t)reward + nt_value<L>(nt_pack(after), lay, tables);
+}
+
+// the best score over the legal moves of `child` (act's), 0 where it has none
+template <int L>
+R48_HD float nt_leaf(const Board &child, const NtLayout &lay, const float *__restrict__ tables)
+{
+    const Moves4 m = move_rows4<true>(child);
+    const uint32_t lg = nt_legal4(m, child);
+    float best = 0.0f;
+    bool have = false;
+    R48_NO_UNROLL
+    for (uint32_t a = 0; a < 4u; a++) {
+        if (!((lg >> a) & 1u))
+            continue;
+        const float s = nt_score<L>(nt_pick(m, a), nt_pick_reward(m, a), lay, tables);
+        if (!have || s > best) {
+            have = true;
+            best = s;
+        }
+    }
+    return best;
+}
+
+// x_c of the contract: 9 leaf(s[c <- 1]) + leaf(s[c <- 2]), +0 where cell c of s holds a tile
+template <int L>
+R48_HD float nt_cell_term(const Board &s, uint32_t c, const NtLayout &lay, const float *__restrict__ tables)
+{
+    if (nt_cell(s, c) != 0u)
+        return 0.0f;
+    float two = 0.0f, four = 0.0f;
+    R48_NO_UNROLL
+    for (uint32_t e = 1; e <= 2u; e++) {
+        Board child = s;
+        place(child, c, e, true);
+        const float leaf = nt_leaf<L>(child, lay, tables);
+        two = e == 1u ? leaf : two;
+        four = leaf;
+    }
+    return nt_fma(9.0f, two, four);
+}
+
+// position of the k-th set bit of m (k counted from 0, k < popcount(m)): a binary search by popcounts
+R48_HD uint32_t nt_select_bit(uint64_t m, uint32_t k)
+{
+    uint32_t w = (uint32_t)m, pos = 0u;
+    const uint32_t c = popc(w);
+    if (k >= c) {
+        k -= c;
+        w = (uint32_t)(m >> 32);
+        pos = 32u;
+    }
+    R48_UNROLL
+    for (uint32_t sh = 16u; sh >= 1u; sh >>= 1) {
+        const uint32_t low = w & ((1u << sh) - 1u);
+        const uint32_t cnt = popc(low);
+        const bool up = k >= cnt;
+        k -= up ? cnt : 0u;
+        w = up ? (w >> sh) : low;
+        pos += up ? sh : 0u;
+    }
+    return pos;
+}
+
+// Q(a) at depth 2 from the reward, S_a and |E| (>= 1 after a legal move)
+R48_HD float nt_q2(uint32_t reward, float s_a, uint32_t n_empty)
+{
+    return (float)(int32_t)reward + s_a / (float)(10u * n_empty);
+}
+
+// first maximiser of four scores; 0 where all are -inf
+R48_HD uint32_t nt_argmax4(float q0, float q1, float q2, float q3)
+{
+    uint32_t a = 0u;
+    float best = q0;
+    if (q1 > best) {
+        best = q1;
+        a = 1u;
+    }
+    if (q2 > best) {
+        best = q2;
+        a = 2u;
+    }
+    if (q3 > best)
+        a = 3u;
+    return a;
+}
+
+// the contract's sum of sixteen cell terms, on the host: the butterfly's levels one after another
+inline float nt_sum16(const float *x)
+{
+    float v[16], w[16];
+    for (int c = 0; c < 16; c++)
+        v[c] = x[c];
+    for (int d = 1; d < 16; d <<= 1) {
+        for (int c = 0; c < 16; c++)
+            w[c] = v[c] + v[c ^ d];
+        for (int c = 0; c < 16; c++)
+            v[c] = w[c];
+    }
+    return v[0];
+}
+
+// The whole search of one board, serially: the host's restatement of k_nt_search, which runs the
+// same nt_leaf / nt_fma / nt_q2 / nt_argmax4 but spreads the children over the lanes of a wave
+// and sums with the butterfly. Returns the action; q[4] and legal as the kernel writes them.
+template <int L>
+inline uint32_t nt_search_board(const Board &b, const NtLayout &lay, const float *tables, int depth, float q[4],
+                                uint32_t &legal)
+{
+    const Moves4 m = move_rows4<true>(b);
+    legal = nt_legal4(m, b);
+    for (uint32_t a = 0; a < 4u; a++) {
+        q[a] = -__builtin_inff();
+        if (!((legal >> a) & 1u))
+            continue;
+        const Board s = nt_pick(m, a);
+        const uint32_t r = nt_pick_reward(m, a);
+        if (depth == 1) {
+            q[a] = nt_score<L>(s, r, lay, tables);
+            continue;
+        }
+        float x[16];
+        for (uint32_t c = 0; c < 16u; c++)
+            x[c] = nt_cell_term<L>(s, c, lay, tables);
+        q[a] = nt_q2(r, nt_sum16(x), blanks(s).n);
+    }
+    return nt_argmax4(q[0], q[1], q[2], q[3]);
 }
 
 }  // namespace r48

@@ -12,7 +12,9 @@
 //   k_nt_apply       every hit again: the one lane whose exchange takes the entry's count also
 //                    takes its sum and moves tables[e] by step * mean delta, once; both scratch
 //                    words are zero afterwards. No float atomics: bitwise reproducible.
-// One board per lane, one 16-byte board load; templated on the tuple length L so the cell loops
+//   k_nt_search      board -> the four action values Q and their first argmax at depth 1 (act's
+//                    scores) or depth 2 (expectimax over the tile spawn); one board per WAVE
+// Otherwise one board per lane, one 16-byte board load; templated on the tuple length L so the cell loops
 // unroll; the expanded layout travels by value in the kernel arguments (wave-uniform).
 #include <hip/hip_runtime.h>
 
@@ -160,6 +162,87 @@ __global__ __launch_bounds__(kBlock) void k_nt_apply(const int8_t *__restrict__ 
     }
 }
 
+// The expectimax search of r48_ntuple.h, one board per wave: lane = 16 a + c is (move a, cell c).
+// Every lane makes the board's four moves (the same registers in all 64 lanes) and keeps its
+// row's afterstate s_a. Depth 2: lane (a, c) is a SLOT when a is legal and cell c of s_a is empty;
+// a slot has two children, s_a[c <- 1] and s_a[c <- 2]. The children of the wave (2 to 120,
+// ~35 on boards of running games) are packed densely over the lanes instead of being evaluated
+// by their own slot's lane: with the slots' ballot in M, child j is spawn e = 1 + (j & 1) in the
+// slot of rank j >> 1 (nt_select_bit finds it; any lane can build any child, it holds all four
+// afterstates), lane l evaluates child l and, where there are more than 64, child l + 64
+// (nt_leaf: move_rows4 + nt_value per legal reply). The slot's lane then reads its two leaves
+// back (ds_bpermute) and forms the header's x_c = fmaf(9, leaf1, leaf2); every other lane holds
+// +0, and S_a is the xor butterfly over the 16 lanes of the row -- the header's fixed order,
+// whichever lane evaluated a leaf, no LDS. Against one slot per lane evaluating both of its
+// children (27 % of the lanes busy, two leaves deep) the packing measured 1.58x / 1.33x faster
+// at 2^16 boards (lines-squares / 4x6) and 1.10x / 1.07x at 4,096, the same bits (DESIGN.md
+// section 16). At depth 1 the first lane of a row evaluates s_a itself. The four row scores are
+// read from lanes 0, 16, 32, 48; those lanes write q, lane 0 the action and the legal set.
+constexpr int kSearchBoards = kBlock / 64;   // boards (waves) per workgroup
+
+template <int L, int DEPTH>
+__global__ __launch_bounds__(kBlock) void k_nt_search(const int8_t *__restrict__ boards, int64_t n,
+                                                      const r48::NtLayout lay, const float *__restrict__ tables,
+                                                      int8_t *__restrict__ actions, float *__restrict__ q,
+                                                      uint8_t *__restrict__ legal)
+{
+    static_assert(DEPTH == 1 || DEPTH == 2, "depth 1 or 2");
+    const int64_t i = (int64_t)blockIdx.x * kSearchBoards + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (i >= n)
+        return;   // the whole wave
+    const uint32_t lane = threadIdx.x & 63u, a = lane >> 4, c = lane & 15u;
+    const r48::Board b = r48::load_board(boards, i);
+    const r48::Moves4 m = r48::move_rows4<true>(b);
+    const uint32_t lg = r48::nt_legal4(m, b);
+    const r48::Board s = r48::nt_pick(m, a);
+    const uint32_t r = r48::nt_pick_reward(m, a);
+    const bool ok = ((lg >> a) & 1u) != 0u;
+    float qa;
+    if (DEPTH == 1) {
+        float x = 0.0f;
+        if (ok && c == 0u)
+            x = r48::nt_score<L>(s, r, lay, tables);
+        qa = __shfl(x, (int)(lane & 48u));
+    } else {
+        const bool slot = ok && r48::nt_cell(s, c) == 0u;
+        const uint64_t M = __ballot(slot);
+        const uint32_t kids = 2u * (uint32_t)__popcll(M);
+        const uint32_t rank2 = 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
+        float leaf0 = 0.0f, leaf1 = 0.0f;
+#pragma unroll 1
+        for (uint32_t base = 0u; base < kids; base += 64u) {   // uniform: at most two rounds
+            float leaf = 0.0f;
+            if (base + lane < kids) {
+                const uint32_t p = r48::nt_select_bit(M, (base + lane) >> 1);
+                r48::Board child = r48::nt_pick(m, p >> 4);
+                r48::place(child, p & 15u, 1u + (lane & 1u), true);
+                leaf = r48::nt_leaf<L>(child, lay, tables);
+            }
+            leaf0 = base == 0u ? leaf : leaf0;
+            leaf1 = base == 0u ? leaf1 : leaf;
+        }
+        const int src = (int)(rank2 & 63u);
+        const float two0 = __shfl(leaf0, src), four0 = __shfl(leaf0, src + 1);
+        const float two1 = __shfl(leaf1, src), four1 = __shfl(leaf1, src + 1);
+        const bool late = rank2 >= 64u;
+        float x = slot ? r48::nt_fma(9.0f, late ? two1 : two0, late ? four1 : four0) : 0.0f;
+        x += __shfl_xor(x, 1);
+        x += __shfl_xor(x, 2);
+        x += __shfl_xor(x, 4);
+        x += __shfl_xor(x, 8);
+        qa = r48::nt_q2(r, x, r48::blanks(s).n);
+    }
+    qa = ok ? qa : -__builtin_inff();
+    const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
+    if (q && c == 0u)
+        q[4 * i + a] = qa;
+    if (lane == 0u) {
+        actions[i] = (int8_t)r48::nt_argmax4(q0, q1, q2, q3);
+        if (legal)
+            legal[i] = (uint8_t)lg;
+    }
+}
+
 // the arguments every entry point shares: boards, n, the layout
 int check_common(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
                  r48::NtLayout &lay)
@@ -211,6 +294,42 @@ int r48_ntuple_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_
         return R48_OK;
     R48_NT_DISPATCH(k_nt_act, boards, n, lay, tables, actions, after, value, reward, legal)
     return launched("k_nt_act");
+}
+
+int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                      int32_t depth, int8_t *actions, float *q, uint8_t *legal, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_common("r48_ntuple_search", boards, n, cells, m, L, lay))
+        return rc;
+    if (depth != 1 && depth != 2)
+        return fail(R48_EINVAL, "r48_ntuple_search: depth must be 1 or 2, got " + std::to_string(depth));
+    if (!tables || !actions || !aligned(tables, 4) || !aligned(q, 4))
+        return fail(R48_EINVAL, "r48_ntuple_search: tables/actions NULL, or tables / q not 4-byte aligned");
+    const int64_t blocks = n / kSearchBoards + (n % kSearchBoards ? 1 : 0);   // one board per wave
+    if (blocks > 0x7FFFFFFFll)
+        return fail(R48_EINVAL, "r48_ntuple_search: n = " + std::to_string(n) + " boards exceed the grid (" +
+                                    std::to_string(kSearchBoards) + " boards per workgroup, 2^31 - 1 workgroups)");
+    if (n == 0)
+        return R48_OK;
+    const dim3 grid((unsigned)blocks), block(kBlock);
+    const hipStream_t st = (hipStream_t)stream;
+#define R48_NT_SEARCH(LEN)                                                                                         \
+    case LEN:                                                                                                      \
+        if (depth == 1)                                                                                            \
+            hipLaunchKernelGGL((k_nt_search<LEN, 1>), grid, block, 0, st, boards, n, lay, tables, actions, q, legal); \
+        else                                                                                                       \
+            hipLaunchKernelGGL((k_nt_search<LEN, 2>), grid, block, 0, st, boards, n, lay, tables, actions, q, legal); \
+        break;
+    switch (lay.L) {
+        R48_NT_SEARCH(2)
+        R48_NT_SEARCH(3)
+        R48_NT_SEARCH(4)
+        R48_NT_SEARCH(5)
+        R48_NT_SEARCH(6)
+    }
+#undef R48_NT_SEARCH
+    return launched("k_nt_search");
 }
 
 int r48_ntuple_accumulate(const int8_t *boards, int64_t n, const float *delta, const uint8_t *valid,

@@ -110,10 +110,33 @@ class NTupleNet:
         self.accumulate(afterstates, delta, valid)
         self.apply(afterstates, alpha / (8.0 * self.m), valid)
 
-    def policy(self):
-        """`policy(boards, t) -> actions` for evaluate.play_episodes: the fused greedy search."""
-        def policy(boards, t):
-            return self.act(boards.contiguous())[0]
+    def search(self, boards, depth=2, actions=None, q=None, legal=None):
+        """Expectimax over the afterstate values -> (actions int8 [n], q float32 [n, 4], legal uint8
+        [n]). depth 1: q[a] = reward + V(afterstate), act's scores. depth 2: q[a] = reward + the mean
+        over the tile spawns (every empty cell, a 2 with weight 0.9, a 4 with 0.1) of act's best
+        score on the board after the spawn, 0 where that board has no move. Illegal moves have q =
+        -inf; the action is the first maximiser, 0 where no move is legal. One board per wave."""
+        if depth not in (1, 2):
+            raise ValueError("search depth is 1 or 2, got %r" % (depth,))
+        n = _boards(boards)
+        actions = _out(actions, "actions", torch.int8, (n,), boards)
+        q = _out(q, "q", torch.float32, (n, 4), boards)
+        legal = _out(legal, "legal", torch.uint8, (n,), boards)
+        check(self._lib.r48_ntuple_search(ptr(boards), n, *self._lay(), ptr(self.tables), depth, ptr(actions), ptr(q),
+                                          ptr(legal), _stream(boards)))
+        return actions, q, legal
+
+    def policy(self, depth=1):
+        """`policy(boards, t) -> actions` for evaluate.play_episodes: the fused greedy search (depth
+        1, act) or the 2-ply expectimax search (depth 2)."""
+        if depth not in (1, 2):
+            raise ValueError("policy depth is 1 or 2, got %r" % (depth,))
+        if depth == 1:
+            def policy(boards, t):
+                return self.act(boards.contiguous())[0]
+        else:
+            def policy(boards, t):
+                return self.search(boards.contiguous(), 2)[0]
         return policy
 
     def state_dict(self):
@@ -184,5 +207,5 @@ class NTupleTrainer:
         self.prev_valid.copy_(self.legal != 0)   # an afterstate exists where a move did
         self.updates += 1
 
-    def policy(self):
-        return self.net.policy()
+    def policy(self, depth=1):
+        return self.net.policy(depth)
