@@ -658,6 +658,27 @@ int r48_ntuple_accumulate(const int8_t *boards, int64_t n, const float *delta, c
 int r48_ntuple_apply(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
                      int32_t L, float step, float *tables, int64_t *acc, uint32_t *cnt, void *stream);
 
+/* apply with temporal-coherence (TC) learning rates. tc_e and tc_a are float[m][16^L] like tables,
+ * zero before the first update: E[e] is the running sum of the mean deltas entry e was updated
+ * with, A[e] the running sum of their absolute values. For every entry hit, with mean =
+ * acc[e] * 2^-16 / cnt[e] as in apply:
+ *     rate       = A[e] > 0 ? fminf(fabsf(E[e]) / A[e], 1) : 1
+ *     tables[e] += step * (rate * mean);  E[e] += mean;  A[e] += fabsf(mean)
+ * fp32. With rate == 1 (no history, or errors of one sign) the table moves by the bits apply moves
+ * it by. One lane owns an entry's three words per launch, as in apply: no float atomics, all three
+ * tables bitwise reproducible and independent of the boards' order; entries not hit keep their
+ * bits; acc and cnt are zero afterwards. R48_EINVAL as for apply, and for NULL or misaligned
+ * tc_e / tc_a. */
+int r48_ntuple_apply_tc(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
+                        int32_t L, float step, float *tables, float *tc_e, float *tc_a, int64_t *acc,
+                        uint32_t *cnt, void *stream);
+
+/* Read-only: rate_out[i] = the mean of rate(e) (above) over board i's 8m hits, fp32, summed in
+ * r48_ntuple_value's order and divided by 8m once. 1 on a network without history. R48_EINVAL for
+ * NULL or misaligned (4 bytes) tc_e / tc_a / rate_out. */
+int r48_ntuple_tc_rate(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                       const float *tc_e, const float *tc_a, float *rate_out, void *stream);
+
 /* Thread-local message of the last failed call on this thread ("" if none). */
 const char *r48_last_error(void);
 /* "rein48 <version> gfx950" */

@@ -138,6 +138,8 @@ SIGNATURES = {
     "r48_ntuple_search": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
     "r48_ntuple_accumulate": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "r48_ntuple_apply": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P]),
+    "r48_ntuple_apply_tc": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "r48_ntuple_tc_rate": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _P]),
     "r48_last_error": (C.c_char_p, []),
     "r48_version": (C.c_char_p, []),
 }

@@ -9,7 +9,7 @@ is bit-identical to training that never stopped (tests/test_checkpoint_gpu.py):
               Adam's m, v and step, the env's boards and counters, the env-step count, the update
               count, and the HBM replay ring (its counters and, unless replay=False, its contents in
               slot order: 38 B per stored transition)
-  NTupleTrainer  the tables, the env's boards and counters, the previous step's afterstates, values,
+  NTupleTrainer  the tables (with cfg.tc also the error sums tc_e / tc_a), the env's boards and counters, the previous step's afterstates, values,
               done and valid flags, and the step count (the update is deterministic: integer
               atomics, one plain table update per entry)
 Draws are keyed by counters, not by RNG state in memory, so restoring the
@@ -41,7 +41,7 @@ _MATCH_FIELDS = {
     "a3c": ("n_boards", "max_steps", "net", "seed", "mode", "features", "bf16"),
     "dqn": ("n_boards", "replay_capacity", "channels", "blocks", "bn", "bf16", "seed", "reward_transform",
             "mask_illegal"),
-    "ntuple": ("n_boards", "seed"),     # and the layout's cells, compared as cells (a name or a list in cfg)
+    "ntuple": ("n_boards", "seed", "tc"),   # and the layout's cells, compared as cells (a name or a list in cfg)
 }
 
 
@@ -125,6 +125,8 @@ def save(trainer, path, replay=True):
         st.update(cfg=cfg, cells=_cells(trainer.net), tables=_cpu(trainer.net.tables), env=_env_state(trainer.env),
                   prev_after=_cpu(trainer.prev_after), prev_value=_cpu(trainer.prev_value),
                   prev_done=_cpu(trainer.prev_done), prev_valid=_cpu(trainer.prev_valid))
+        if trainer.cfg.tc:
+            st.update(tc_e=_cpu(trainer.net.tc_e), tc_a=_cpu(trainer.net.tc_a))
     elif kind == "a3c":
         st.update(net=_cpu_state(trainer.net), ms=_cpu(trainer.opt.ms), mom=_cpu(trainer.opt.mom),
                   env=_env_state(trainer.env), sample_ctr=int(trainer.sample_ctr))
@@ -171,6 +173,9 @@ def load(trainer, path):
     with torch.no_grad():
         if kind == "ntuple":
             trainer.net.tables.copy_(st["tables"].to(dev))
+            if trainer.cfg.tc:
+                trainer.net.tc_e.copy_(st["tc_e"].to(dev))
+                trainer.net.tc_a.copy_(st["tc_a"].to(dev))
             _load_env(trainer.env, st["env"])
             for k in ("prev_after", "prev_value", "prev_done", "prev_valid"):
                 getattr(trainer, k).copy_(st[k].to(dev))

@@ -171,6 +171,63 @@ R48_HD float nt_value(const NtBoard &b, const NtLayout &lay, const float *__rest
     return sum;
 }
 
+// ---- temporal-coherence learning rates ---------------------------------------------------------
+// Every table entry e keeps E[e], the running sum of the mean errors it was updated with, and
+// A[e], the running sum of their absolute values (float[m][16^L] like the tables, zero at the
+// start). It learns at rate |E| / A: 1 while its errors agree in sign, towards 0 once they turn
+// to noise (Beal & Smith; Jaskowski 2016). For an entry hit in an update, with mean = the
+// update's mean delta of its hits (nt_mean, the expression plain apply uses):
+//     rate       = A[e] > 0 ? fminf(fabsf(E[e]) / A[e], 1) : 1
+//     tables[e] += step * (rate * mean)
+//     E[e]      += mean
+//     A[e]      += fabsf(mean)
+// fp32 throughout. rate * mean is formed first, so with rate == 1 the table moves by the bits
+// plain apply moves it by: TC without history is TD.
+
+// the mean delta of an entry's hits from the update's scratch: acc counts 2^-16, cnt the hits
+R48_HD float nt_mean(long long acc, uint32_t cnt)
+{
+    return ((float)acc * (1.0f / 65536.0f)) / (float)cnt;
+}
+
+R48_HD float nt_tc_rate(float e, float a)
+{
+    return a > 0.0f ? __builtin_fminf(__builtin_fabsf(e) / a, 1.0f) : 1.0f;
+}
+
+// one entry's update, in place
+R48_HD void nt_tc_update(float &table, float &e, float &a, float mean, float step)
+{
+    const float rate = nt_tc_rate(e, a);
+    table += step * (rate * mean);
+    e += mean;
+    a += __builtin_fabsf(mean);
+}
+
+// The mean of rate(e) over the board's 8m hits: fp32, summed from 0 in nt_value's order
+// p = 0 .. 8m - 1, one division by (float)(8m) at the end. The loads of one tuple's hits (8 of E,
+// 8 of A) are issued before their rates are formed.
+template <int L>
+R48_HD float nt_tc_rate_mean(const NtBoard &b, const NtLayout &lay, const float *__restrict__ tc_e,
+                             const float *__restrict__ tc_a)
+{
+    const int np = kNtSyms * lay.m;
+    float sum = 0.0f;
+    for (int p = 0; p < np; p += kNtSyms) {
+        float e[kNtSyms], a[kNtSyms];
+        R48_UNROLL
+        for (int j = 0; j < kNtSyms; j++) {
+            const uint32_t at = nt_entry<L>(b, lay, p + j);
+            e[j] = tc_e[at];
+            a[j] = tc_a[at];
+        }
+        R48_UNROLL
+        for (int j = 0; j < kNtSyms; j++)
+            sum += nt_tc_rate(e[j], a[j]);
+    }
+    return sum / (float)np;
+}
+
 // ---- the search -------------------------------------------------------------------------------
 
 #if defined(__HIPCC__)

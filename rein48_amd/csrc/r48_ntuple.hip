@@ -12,6 +12,9 @@
 //   k_nt_apply       every hit again: the one lane whose exchange takes the entry's count also
 //                    takes its sum and moves tables[e] by step * mean delta, once; both scratch
 //                    words are zero afterwards. No float atomics: bitwise reproducible.
+//   k_nt_apply_tc    apply with temporal-coherence learning rates: the owner lane also owns the
+//                    entry's error sums E[e], A[e] and scales its step by |E| / A
+//   k_nt_tc_rate     board -> the mean learning rate |E| / A over its 8m hits (read-only)
 //   k_nt_search      board -> the four action values Q and their first argmax at depth 1 (act's
 //                    scores) or depth 2 (expectimax over the tile spawn); one board per WAVE
 // Otherwise one board per lane, one 16-byte board load; templated on the tuple length L so the cell loops
@@ -160,6 +163,52 @@ __global__ __launch_bounds__(kBlock) void k_nt_apply(const int8_t *__restrict__ 
             }
         }
     }
+}
+
+// apply with temporal-coherence learning rates (r48_ntuple.h): the lane that takes an entry's
+// count owns tables[e], E[e] and A[e] for this launch. Its three loads are issued together, the
+// rule runs in registers, three plain stores follow. The sums are order-free integers and the
+// owner's arithmetic does not depend on which lane it is, so all three tables are bitwise
+// reproducible and independent of the boards' order in the batch.
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_apply_tc(const int8_t *__restrict__ boards, int64_t n,
+                                                        const uint8_t *__restrict__ valid, const r48::NtLayout lay,
+                                                        float step, float *__restrict__ tables,
+                                                        float *__restrict__ tc_e, float *__restrict__ tc_a,
+                                                        unsigned long long *__restrict__ acc,
+                                                        uint32_t *__restrict__ cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || (valid && !valid[i]))
+        return;
+    const r48::NtBoard b = r48::nt_pack(r48::load_board(boards, i));
+    for (int t = 0; t < lay.m; t++) {
+#pragma unroll
+        for (int g = 0; g < r48::kNtSyms; g++) {
+            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g);
+            const uint32_t c = atomicExch(&cnt[e], 0u);
+            if (c != 0u) {
+                float w = tables[e], se = tc_e[e], sa = tc_a[e];
+                const long long a = (long long)atomicExch(&acc[e], 0ull);
+                r48::nt_tc_update(w, se, sa, r48::nt_mean(a, c), step);
+                tables[e] = w;
+                tc_e[e] = se;
+                tc_a[e] = sa;
+            }
+        }
+    }
+}
+
+// How settled the network is on a set of boards: the mean learning rate over each board's hits.
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_tc_rate(const int8_t *__restrict__ boards, int64_t n,
+                                                       const r48::NtLayout lay, const float *__restrict__ tc_e,
+                                                       const float *__restrict__ tc_a, float *__restrict__ rate_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    rate_out[i] = r48::nt_tc_rate_mean<L>(r48::nt_pack(r48::load_board(boards, i)), lay, tc_e, tc_a);
 }
 
 // The expectimax search of r48_ntuple.h, one board per wave: lane = 16 a + c is (move a, cell c).
@@ -360,6 +409,38 @@ int r48_ntuple_apply(const int8_t *boards, int64_t n, const uint8_t *valid, cons
         return R48_OK;
     R48_NT_DISPATCH(k_nt_apply, boards, n, valid, lay, step, tables, reinterpret_cast<unsigned long long *>(acc), cnt)
     return launched("k_nt_apply");
+}
+
+int r48_ntuple_apply_tc(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
+                        int32_t L, float step, float *tables, float *tc_e, float *tc_a, int64_t *acc, uint32_t *cnt,
+                        void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_common("r48_ntuple_apply_tc", boards, n, cells, m, L, lay))
+        return rc;
+    if (!tables || !tc_e || !tc_a || !acc || !cnt || !aligned(tables, 4) || !aligned(tc_e, 4) || !aligned(tc_a, 4) ||
+        !aligned(acc, 8) || !aligned(cnt, 4))
+        return fail(R48_EINVAL, "r48_ntuple_apply_tc: tables/tc_e/tc_a/acc/cnt NULL, acc not 8-byte aligned, or "
+                                "tables / tc_e / tc_a / cnt not 4-byte aligned");
+    if (n == 0)
+        return R48_OK;
+    R48_NT_DISPATCH(k_nt_apply_tc, boards, n, valid, lay, step, tables, tc_e, tc_a,
+                    reinterpret_cast<unsigned long long *>(acc), cnt)
+    return launched("k_nt_apply_tc");
+}
+
+int r48_ntuple_tc_rate(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tc_e,
+                       const float *tc_a, float *rate_out, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_common("r48_ntuple_tc_rate", boards, n, cells, m, L, lay))
+        return rc;
+    if (!tc_e || !tc_a || !rate_out || !aligned(tc_e, 4) || !aligned(tc_a, 4) || !aligned(rate_out, 4))
+        return fail(R48_EINVAL, "r48_ntuple_tc_rate: tc_e/tc_a/rate_out NULL or not 4-byte aligned");
+    if (n == 0)
+        return R48_OK;
+    R48_NT_DISPATCH(k_nt_tc_rate, boards, n, lay, tc_e, tc_a, rate_out)
+    return launched("k_nt_tc_rate");
 }
 
 }  // extern "C"

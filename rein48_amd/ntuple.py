@@ -1,4 +1,5 @@
-"""N-tuple network on afterstates, trained by TD(0) (rein48_amd/csrc/r48_ntuple.hip).
+"""N-tuple network on afterstates, trained by TD(0), optionally with temporal-coherence learning
+rates (rein48_amd/csrc/r48_ntuple.hip).
 
 The value of a board is a sum of lookup-table entries over `m` board patterns (tuples of `L`
 cells) and their 8 symmetries: V(b) = sum_t sum_g tables[t][index(g . b, t)], index = sum_k
@@ -11,6 +12,11 @@ TD-afterstate n-tuple network of Szubert & Jaskowski (CIG 2014) with its per-ent
 normalisation taken over the batch: every table entry moves by alpha / (8m) times the MEAN delta of
 the boards that hit it, so one board alone moves V(s') by alpha * delta and 64 copies of it move it
 by the same amount.
+
+tc=True adds temporal-coherence (TC) learning rates (Beal & Smith; Jaskowski 2016): every entry keeps
+the running sum E of the mean deltas it was updated with and the running sum A of their absolute
+values, and its step is scaled by |E| / A -- 1 while its errors agree in sign, towards 0 once they
+are noise. No step size is annealed by hand; alpha = 1.0 is the recommended setting with it.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -46,9 +52,10 @@ def layout_cells(layout):
 
 class NTupleNet:
     """The tables float32 [m, 16^L] and the update's scratch (acc int64, cnt uint32 held as int32,
-    same shape; zero between calls) on one GPU."""
+    same shape; zero between calls) on one GPU. With tc, also the error sums tc_e and tc_a of the
+    temporal-coherence learning rates (float32, same shape, zero at the start: +512 MiB for "4x6")."""
 
-    def __init__(self, layout="4x6", device="cuda:0"):
+    def __init__(self, layout="4x6", device="cuda:0", tc=False):
         self.cells = layout_cells(layout)
         self.m, self.L = len(self.cells), len(self.cells[0])
         self.device = torch.device(device)
@@ -60,6 +67,9 @@ class NTupleNet:
         self.tables = torch.zeros((self.m, size), dtype=torch.float32, device=self.device)
         self.acc = torch.zeros((self.m, size), dtype=torch.int64, device=self.device)
         self.cnt = torch.zeros((self.m, size), dtype=torch.int32, device=self.device)
+        self.tc = bool(tc)
+        self.tc_e = torch.zeros((self.m, size), dtype=torch.float32, device=self.device) if self.tc else None
+        self.tc_a = torch.zeros((self.m, size), dtype=torch.float32, device=self.device) if self.tc else None
         self._lib = _lib.load()
 
     def _lay(self):
@@ -97,18 +107,36 @@ class NTupleNet:
                                               ptr(self.cnt), _stream(boards)))
 
     def apply(self, boards, step, valid=None):
-        """Second half: every entry the boards hit moves by step * its mean delta; scratch back to zero."""
+        """Second half: every entry the boards hit moves by step * its mean delta (a TC net: times
+        its rate |E| / A, and E, A take the mean delta in); scratch back to zero."""
         n = _boards(boards)
         if valid is not None and _dev(valid, "valid", torch.uint8).numel() != n:
             raise ValueError("valid must have one element per board (%d)" % n)
+        if self.tc:
+            check(self._lib.r48_ntuple_apply_tc(ptr(boards), n, ptr(valid), *self._lay(), float(step),
+                                                ptr(self.tables), ptr(self.tc_e), ptr(self.tc_a), ptr(self.acc),
+                                                ptr(self.cnt), _stream(boards)))
+            return
         check(self._lib.r48_ntuple_apply(ptr(boards), n, ptr(valid), *self._lay(), float(step), ptr(self.tables),
                                          ptr(self.acc), ptr(self.cnt), _stream(boards)))
 
     def td_update(self, afterstates, delta, alpha, valid=None):
         """tables[e] += alpha / (8m) * mean over the valid boards hitting e of delta, for every entry
-        hit. Deterministic: integer atomics, then one plain update per entry."""
+        hit (a TC net: times the entry's rate). Deterministic: integer atomics, then one plain update
+        per entry."""
         self.accumulate(afterstates, delta, valid)
         self.apply(afterstates, alpha / (8.0 * self.m), valid)
+
+    def tc_rate(self, boards, out=None):
+        """float32 [n]: the mean TC learning rate |E| / A over each board's 8m hits (1 on a net
+        without history) -- how settled the network is on these boards. TC nets only."""
+        if not self.tc:
+            raise ValueError("tc_rate needs a net built with tc=True")
+        n = _boards(boards)
+        out = _out(out, "out", torch.float32, (n,), boards)
+        check(self._lib.r48_ntuple_tc_rate(ptr(boards), n, *self._lay(), ptr(self.tc_e), ptr(self.tc_a), ptr(out),
+                                           _stream(boards)))
+        return out
 
     def search(self, boards, depth=2, actions=None, q=None, legal=None):
         """Expectimax over the afterstate values -> (actions int8 [n], q float32 [n, 4], legal uint8
@@ -140,12 +168,20 @@ class NTupleNet:
         return policy
 
     def state_dict(self):
-        return {"cells": [list(t) for t in self.cells], "tables": self.tables.detach().to("cpu", copy=True)}
+        st = {"cells": [list(t) for t in self.cells], "tables": self.tables.detach().to("cpu", copy=True)}
+        if self.tc:
+            st.update(tc_e=self.tc_e.detach().to("cpu", copy=True), tc_a=self.tc_a.detach().to("cpu", copy=True))
+        return st
 
     def load_state_dict(self, st):
         if [list(t) for t in self.cells] != [list(t) for t in st["cells"]]:
             raise ValueError("NTupleNet: the layout is %r, the saved one %r" % (self.cells, st["cells"]))
+        if self.tc and not ("tc_e" in st and "tc_a" in st):
+            raise ValueError("NTupleNet: a tc=True net needs the saved tc_e / tc_a, the state has none")
         self.tables.copy_(st["tables"].to(self.device))
+        if self.tc:
+            self.tc_e.copy_(st["tc_e"].to(self.device))
+            self.tc_a.copy_(st["tc_a"].to(self.device))
 
     def save(self, path):
         torch.save(self.state_dict(), path)
@@ -160,6 +196,7 @@ class NTupleConfig:
     layout: object = "4x6"           # a name in LAYOUTS or a sequence of cell tuples
     alpha: float = 0.25
     seed: int = 0
+    tc: bool = False                 # temporal-coherence learning rates; alpha = 1.0 is recommended with it
 
 
 class NTupleTrainer:
@@ -169,6 +206,7 @@ class NTupleTrainer:
          r_t + v_t; delta = target - v_{t-1}, where v_{t-1} is the value act returned one step ago
          (one batch update old); td_update(s'_{t-1}, delta, alpha, valid)
       3. env.step(a_t, auto_reset=True); s'_t, v_t, done become the "previous"
+    cfg.tc: the update scales every entry's step by its temporal-coherence rate (NTupleNet).
     No exploration: the spawns randomise. Single GPU (an all-reduce of the table updates is not
     built)."""
 
@@ -177,7 +215,7 @@ class NTupleTrainer:
         self.device = torch.device(device)
         self.rank = 0
         n = cfg.n_boards
-        self.net = NTupleNet(cfg.layout, self.device)
+        self.net = NTupleNet(cfg.layout, self.device, tc=cfg.tc)
         self.env = VecGame(n, device=self.device, seed=cfg.seed)
         self.device = self.env.device
         self.env.reset()

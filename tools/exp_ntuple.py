@@ -2,6 +2,7 @@
 
     python tools/exp_ntuple.py [--out DIR] [--sizes 65536,1048576] [--scores]
     python tools/exp_ntuple.py --search [--out DIR] [--sizes 4096,65536] [--scores] [--long]
+    python tools/exp_ntuple.py --tc [--out DIR] [--sizes 65536,1048576] [--scores]
 
 For both named layouts and each board count: device-event times (5 warm-up calls, median of 7
 windows of 20 calls) of value, act, accumulate and apply with their table loads or atomics per
@@ -22,6 +23,16 @@ every legal afterstate laid out by torch -> act on the children -> torch reducti
 (c) picks the fused search's action. With --scores: whole-episode scores of policy(depth=1) against
 policy(depth=2) on the same trained tables (1,024 x 2,000 steps for both layouts; --long adds 4,096 x
 10,000 for 4x6), 4,096 episodes, eval seed 13. Writes exp_ntuple_search.json under --out.
+
+--tc: temporal-coherence learning rates against plain TD(0). For both layouts and each board count,
+device-event times in one process with alternated windows (TD window, TC window, TD window, ...;
+5 warm-up calls each, median of 7 windows of 20 calls): accumulate + apply on a tc=False net against
+accumulate + apply_tc on a tc=True net (the same boards and deltas; apply and apply_tc derived by
+subtracting accumulate alone, as above), tc_rate next to value, and a whole train_step of a TD
+trainer against a TC one -- once with alpha 0 for both (frozen zero tables: the two play the same
+games, so each pair of windows sees the same boards) and once with the recipes' alphas. With --scores: TD(0) alpha 0.25 against TC alpha 1.0 at depth 1 and 2 for
+lines-squares and 4x6 at 1,024 x 2,000 steps and 4x6 at 4,096 x 10,000, 4,096 episodes, eval seed
+13, and the 1,024 x 1,000 lines-squares recipe of the learning test. Writes exp_ntuple_tc.json.
 """
 import argparse
 import json
@@ -221,6 +232,137 @@ def search_scores(layout, n_boards, steps, eval_seed=13, episodes=4096):
     return out
 
 
+def alternated_ms(fns, warmup=5, windows=7, calls=20):
+    """event_ms for several callables with their windows interleaved: {name: (median, min, max)}."""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    out = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(calls):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out[k].append(e0.elapsed_time(e1) / calls)
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in out.items()}
+
+
+def _ms(t):
+    return {"ms": t[0], "ms_min": t[1], "ms_max": t[2]}
+
+
+def tc_kernels(layout, n):
+    td, tc = NTupleNet(layout, device=DEV), NTupleNet(layout, device=DEV, tc=True)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    td.tables.copy_(torch.randn(td.tables.shape, generator=g, device=DEV) * 30.0)
+    tc.tables.copy_(td.tables)
+    env = VecGame(n, device=DEV, seed=7)
+    env.reset()
+    greedy = afterstate_policy(None)
+    for t in range(150):
+        env.step(greedy(env.boards, t), auto_reset=True)
+    after = td.act(env.boards.clone())[1]
+    delta = torch.randn(n, generator=g, device=DEV) * 100.0
+    hits = 8 * td.m * n
+    td.accumulate(after, delta)
+    touched = int((td.cnt != 0).sum())
+    td.apply(after, 0.0)
+    res = {"layout": layout, "boards": n, "tuples": td.m, "length": td.L, "hits": hits, "touched_entries": touched,
+           "hits_per_touched_entry": hits / touched}
+    rate, value = torch.empty(n, device=DEV), torch.empty(n, device=DEV)
+    t = alternated_ms({"td": lambda: td.td_update(after, delta, 0.25), "tc": lambda: tc.td_update(after, delta, 1.0),
+                       "value": lambda: td.value(after, out=value), "tc_rate": lambda: tc.tc_rate(after, out=rate)})
+    res["accumulate_apply"], res["accumulate_apply_tc"] = _ms(t["td"]), _ms(t["tc"])
+    res["value"], res["tc_rate"] = _ms(t["value"]), _ms(t["tc_rate"])
+    res["mean_tc_rate_after_timing"] = float(tc.tc_rate(after).mean())
+    med, lo, hi = event_ms(lambda: td.accumulate(after, delta))     # sums grow; the integer adds cost the same
+    td.acc.zero_()
+    td.cnt.zero_()
+    res["accumulate"] = {"ms": med, "ms_min": lo, "ms_max": hi}
+    res["apply"] = {"ms": max(t["td"][0] - med, 1e-6), "derived": "accumulate_apply - accumulate"}
+    res["apply_tc"] = {"ms": max(t["tc"][0] - med, 1e-6), "derived": "accumulate_apply_tc - accumulate"}
+    res["apply_tc_over_apply"] = res["apply_tc"]["ms"] / res["apply"]["ms"]
+    res["pair_tc_over_td"] = t["tc"][0] / t["td"][0]
+    del td, tc
+    torch.cuda.empty_cache()
+    return res
+
+
+def tc_train_step(layout, n, frozen):
+    """frozen: alpha 0 for both, so the tables stay zero, both trainers play the same greedy-merge
+    games from the same seed and every pair of windows sees the same boards -- the like-for-like
+    cost of the step. Otherwise the recipes' alphas (0.25 / 1.0): the two then play different games,
+    and the share of hot entries (patterns of empty cells) differs with them."""
+    trs = {"td": NTupleTrainer(NTupleConfig(n_boards=n, layout=layout, alpha=0.0 if frozen else 0.25, seed=3), device=DEV),
+           "tc": NTupleTrainer(NTupleConfig(n_boards=n, layout=layout, alpha=0.0 if frozen else 1.0, seed=3, tc=True),
+                               device=DEV)}
+    t = alternated_ms({k: tr.train_step for k, tr in trs.items()}, warmup=20)
+    same = bool(torch.equal(trs["td"].env.boards, trs["tc"].env.boards))
+    res = {"layout": layout, "boards": n, "frozen_tables": frozen, "same_boards_at_the_end": same,
+           "train_step_td": _ms(t["td"]), "train_step_tc": _ms(t["tc"]),
+           "tc_over_td": t["tc"][0] / t["td"][0], "env_steps_per_s_td": n / (t["td"][0] * 1e-3),
+           "env_steps_per_s_tc": n / (t["tc"][0] * 1e-3)}
+    del trs
+    torch.cuda.empty_cache()
+    return res
+
+
+def tc_scores(layout, n_boards, steps, eval_seed=13, episodes=4096):
+    out = {"layout": layout, "train_boards": n_boards, "train_steps": steps, "eval_seed": eval_seed, "episodes": episodes}
+    for name, alpha, tc in (("td", 0.25, False), ("tc", 1.0, True)):
+        tr = NTupleTrainer(NTupleConfig(n_boards=n_boards, layout=layout, alpha=alpha, seed=0, tc=tc), device=DEV)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            tr.train_step()
+        torch.cuda.synchronize()
+        row = {"alpha": alpha, "tc": tc, "train_seconds": time.perf_counter() - t0}
+        if tc:
+            row["mean_tc_rate_on_env_boards"] = float(tr.net.tc_rate(tr.env.boards).mean())
+        for depth in (1, 2):
+            ev = play_episodes(tr.policy(depth=depth), episodes, device=DEV, seed=eval_seed, return_scores=True)
+            sc = ev.pop("scores").numpy()
+            ev["score_std"] = float(sc.std(ddof=1))
+            ev["standard_error"] = ev["score_std"] / episodes ** 0.5
+            row["depth%d" % depth] = ev
+        out[name] = row
+        del tr
+        torch.cuda.empty_cache()
+    for depth in ("depth1", "depth2"):
+        a, b = out["tc"][depth], out["td"][depth]
+        se = (a["standard_error"] ** 2 + b["standard_error"] ** 2) ** 0.5
+        out[depth + "_tc_minus_td_in_standard_errors"] = (a["mean_score"] - b["mean_score"]) / se
+        out[depth + "_tc_over_td"] = a["mean_score"] / b["mean_score"]
+    return out
+
+
+def main_tc(args):
+    out = {"device": torch.cuda.get_device_name(0), "kernels": [], "train_step": [], "scores": []}
+    for layout in ("lines-squares", "4x6"):
+        for n in (int(s) for s in (args.sizes or "65536,1048576").split(",")):
+            r = tc_kernels(layout, n)
+            out["kernels"].append(r)
+            print(json.dumps(r), flush=True)
+            for frozen in (True, False):
+                r = tc_train_step(layout, n, frozen)
+                out["train_step"].append(r)
+                print(json.dumps(r), flush=True)
+    if args.scores:
+        for layout, n_boards, steps, episodes, seed in (("lines-squares", 1024, 1000, 512, 1), ("lines-squares", 1024, 2000, 4096, 13),
+                                                        ("4x6", 1024, 2000, 4096, 13), ("4x6", 4096, 10000, 4096, 13)):
+            r = tc_scores(layout, n_boards, steps, eval_seed=seed, episodes=episodes)
+            out["scores"].append(r)
+            print(json.dumps(r), flush=True)
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        with open(os.path.join(args.out, "exp_ntuple_tc.json"), "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main_search(args):
     out = {"device": torch.cuda.get_device_name(0), "kernels": [], "scores": []}
     for layout in ("lines-squares", "4x6"):
@@ -247,11 +389,14 @@ def main():
     ap.add_argument("--scores", action="store_true")
     ap.add_argument("--search", action="store_true")
     ap.add_argument("--long", action="store_true")
+    ap.add_argument("--tc", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("exp_ntuple.py needs a GPU")
     if args.search:
         return main_search(args)
+    if args.tc:
+        return main_tc(args)
     args.sizes = args.sizes or "65536,1048576"
     out = {"device": torch.cuda.get_device_name(0), "kernels": [], "train_step": [], "scores": []}
     for layout in ("lines-squares", "4x6"):
