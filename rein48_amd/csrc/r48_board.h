@@ -597,4 +597,14 @@ R48_HD void reset_board(Board &r, uint32_t cell, bool four)
     place(r, cell & 15u, four ? 2u : 1u, true);
 }
 
+// The auto-reset board already in the line form of action a (`cell` counts in rows, as in
+// reset_board): a one-tile board again, so a kernel that tracks orientations can reset a board
+// without taking it back to rows (k_step_n's 128-entry LDS table, r48_env.hip).
+R48_HD Board reset_lines(uint32_t a, uint32_t cell, bool four)
+{
+    Board r;
+    reset_board(r, cell, four);
+    return reorient(r, kOrient[a & 3u]);   // kOrient[4 * UP + a]: rows -> line form of a
+}
+
 }  // namespace r48

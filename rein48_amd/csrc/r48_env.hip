@@ -29,6 +29,9 @@ constexpr int kBlock = 256;
 #define R48_STEPN_NP 1
 #endif
 constexpr int kStepNP = R48_STEPN_NP;   // board pairs per lane in k_step_n (A/B builds: -DR48_STEPN_NP=2)
+#ifndef R48_STEPN_LOOP_PAD
+#define R48_STEPN_LOOP_PAD 1   // s_nops in front of k_step_n's step loop (A/B builds: -DR48_STEPN_LOOP_PAD=0..15)
+#endif
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -131,10 +134,17 @@ __device__ __forceinline__ LaneOut step_lane(Board b, uint32_t a_given, Draw d, 
 
 // ---------------------------------------------------------------- orientation-tracked step
 // k_step_n keeps each board in the line form of its last action (r48_board.h "Orientations"):
-// `ob` = 64 x that action (0 = rows, after a load or a reset), so the selector record taking the
-// board to the line form of action a sits at byte ob + 16a of the 256-byte LDS table. A step is
-// then one reorient (8 v_perm) + step_lines -- no to_lines / from_lines round trip, no per-lane
-// selects on the action -- and the boards go back to rows once, when the call ends.
+// `ob` = 64 x that action (0 = rows, after a load), so the selector record taking the board to the
+// line form of action a sits at byte ob + 16a of the 256-byte LDS table. A step is then one
+// reorient (8 v_perm) + step_lines -- no to_lines / from_lines round trip, no per-lane selects on
+// the action -- and the boards go back to rows once, when the call ends.
+// Auto-reset (RESET_TAB, every AUTO_RESET k_step_n): a reset board is one tile on an empty board,
+// and so is its image in any line form, so a finished board is replaced by the reset board ALREADY
+// in the line form of the step's action -- r48::reset_lines(a, cell, four), read from a 128-entry
+// x 16-byte LDS table at entry (a << 5) | (four << 4) | cell. The board never goes back to rows
+// inside the loop, `ob` and any selector record read ahead for the next step stay as they are.
+// k_step (RESET_TAB = false: one step per launch, HBM-bound) builds the rows board in registers
+// and sets ob = 0 instead.
 __device__ __forceinline__ r48::Orient orient_at(const r48::Orient *tab, uint32_t off)
 {
     // one ds_read_b128 (the table is 16-byte aligned, off a multiple of 16)
@@ -143,16 +153,34 @@ __device__ __forceinline__ r48::Orient orient_at(const r48::Orient *tab, uint32_
     return r48::Orient{v.x, v.y, v.z, v.w};
 }
 
-__device__ __forceinline__ void load_orient_table(r48::Orient *tab)
+constexpr int kResetEntries = 128;   // (a, four, cell)
+
+// fills the selector table and, if RESET_TAB, the reset table (the block needs >= 128 threads)
+template <bool RESET_TAB>
+__device__ __forceinline__ void load_orient_table(r48::Orient *tab, Board *rtab = nullptr)
 {
     if (threadIdx.x < 16)
         tab[threadIdx.x] = r48::kOrient[threadIdx.x];
+    if (RESET_TAB && threadIdx.x < kResetEntries)
+        rtab[threadIdx.x] = r48::reset_lines(threadIdx.x >> 5, threadIdx.x & 15u, (threadIdx.x >> 4) & 1u);
     __syncthreads();
 }
 
-template <bool RANDOM, bool AUTO_RESET, bool REWARD>
-__device__ __forceinline__ LaneOut step_lane_lines(Board &L, uint32_t &ob, const r48::Orient *tab, uint32_t a_given,
-                                                   Draw d, bool want_score)
+// The auto-reset of one lane inside the wave-uniform `any board done` branch: one ds_read_b128 of
+// the reset board in the line form of the step's action (a9 = 512 x action) and four selects.
+// Every lane reads (the offset is below 2 KiB whatever the draw), only done lanes take the value.
+__device__ __forceinline__ void reset_from_table(Board &L, const Board *rtab, uint32_t a9, uint32_t y, uint32_t done)
+{
+    const uint32_t off = a9 | ((y & 0x0FFFFFFFu) < r48::kFourThresh28 ? 256u : 0u) | ((y >> 28) << 4);
+    const u32x4 z = *reinterpret_cast<const u32x4 *>(
+        __builtin_assume_aligned(reinterpret_cast<const char *>(rtab) + off, 16));
+    L = Board{r48::sel(done, z.x, L.w0), r48::sel(done, z.y, L.w1), r48::sel(done, z.z, L.w2),
+              r48::sel(done, z.w, L.w3)};
+}
+
+template <bool RANDOM, bool AUTO_RESET, bool REWARD, bool RESET_TAB>
+__device__ __forceinline__ LaneOut step_lane_lines(Board &L, uint32_t &ob, const r48::Orient *tab, const Board *rtab,
+                                                   uint32_t a_given, Draw d, bool want_score)
 {
     LaneOut r;
     r.a = RANDOM ? d.x >> 30 : a_given;  // uniform over {UP, DOWN, LEFT, RIGHT} (control/rand.py:9-11)
@@ -167,11 +195,16 @@ __device__ __forceinline__ LaneOut step_lane_lines(Board &L, uint32_t &ob, const
         r.score = r48::tile_sum(L);      // order-free: any orientation
     }
     if (AUTO_RESET && __ballot(o.done) != 0) {
-        Board z;
-        r48::reset_board(z, d.y >> 28, (d.y & 0x0FFFFFFFu) < r48::kFourThresh28);   // rows
-        L = Board{r48::sel(o.done, z.w0, L.w0), r48::sel(o.done, z.w1, L.w1), r48::sel(o.done, z.w2, L.w2),
-                  r48::sel(o.done, z.w3, L.w3)};
-        ob = o.done ? 0u : ob;
+        if (RESET_TAB) {
+            // the orientation is a_given & 3 also for a bad action byte (board unchanged, maybe dead)
+            reset_from_table(L, rtab, a16 << 5, d.y, o.done);
+        } else {
+            Board z;
+            r48::reset_board(z, d.y >> 28, (d.y & 0x0FFFFFFFu) < r48::kFourThresh28);   // rows
+            L = Board{r48::sel(o.done, z.w0, L.w0), r48::sel(o.done, z.w1, L.w1), r48::sel(o.done, z.w2, L.w2),
+                      r48::sel(o.done, z.w3, L.w3)};
+            ob = o.done ? 0u : ob;
+        }
     }
     r.done = o.done;
     r.changed = o.changed;
@@ -180,12 +213,11 @@ __device__ __forceinline__ LaneOut step_lane_lines(Board &L, uint32_t &ob, const
 }
 
 // k_step_n's random-policy step on a board ALREADY reoriented to the line form of this step's
-// action (d.x >> 30). `s_next` holds the caller's read-ahead of the next step's selector record,
-// taken from the line form of this action; boards this step resets are back in rows, so theirs is
-// re-read from the rows entry (offset a16n).
+// action (d.x >> 30). The caller has the next step's selector record (this action -> next action)
+// in flight; a board this step resets stays in the line form of this action (reset_from_table), so
+// that record is the right one for it too and nothing here touches it.
 template <bool AUTO_RESET, bool REWARD>
-__device__ __forceinline__ LaneOut step_lane_pre(Board &L, r48::Orient &s_next, uint32_t a16n, const r48::Orient *tab,
-                                                 Draw d, bool want_score)
+__device__ __forceinline__ LaneOut step_lane_pre(Board &L, const Board *rtab, Draw d, bool want_score)
 {
     LaneOut r;
     r.a = d.x >> 30;
@@ -195,15 +227,8 @@ __device__ __forceinline__ LaneOut step_lane_pre(Board &L, r48::Orient &s_next, 
         asm volatile("" ::: "memory");
         r.score = r48::tile_sum(L);
     }
-    if (AUTO_RESET && __ballot(o.done) != 0) {
-        Board z;
-        r48::reset_board(z, d.y >> 28, (d.y & 0x0FFFFFFFu) < r48::kFourThresh28);   // rows
-        L = Board{r48::sel(o.done, z.w0, L.w0), r48::sel(o.done, z.w1, L.w1), r48::sel(o.done, z.w2, L.w2),
-                  r48::sel(o.done, z.w3, L.w3)};
-        const r48::Orient z0 = orient_at(tab, a16n);
-        s_next = r48::Orient{r48::sel(o.done, z0.x0, s_next.x0), r48::sel(o.done, z0.x1, s_next.x1),
-                             r48::sel(o.done, z0.te, s_next.te), r48::sel(o.done, z0.to, s_next.to)};
-    }
+    if (AUTO_RESET && __ballot(o.done) != 0)
+        reset_from_table(L, rtab, (d.x >> 21) & 0x600u, d.y, o.done);
     r.done = o.done;
     r.changed = o.changed;
     r.reward = o.reward;
@@ -275,7 +300,7 @@ __global__ __launch_bounds__(kBlock) void k_step(int8_t *boards, int64_t n, int6
     const int64_t i = (int64_t)blockIdx.x * kTile + 2 * (int64_t)threadIdx.x;
     const bool want_score = score != nullptr;
     __shared__ __attribute__((aligned(16))) r48::Orient tab[16];
-    load_orient_table(tab);
+    load_orient_table<false>(tab);
     if ((int64_t)(blockIdx.x + 1) * kTile <= n && (gid0 & 1) == 0 &&
         planes_aligned(actions, done, changed, reward, score)) {
         Board be = load_board(boards, i), bo = load_board(boards, i + 1);
@@ -292,8 +317,8 @@ __global__ __launch_bounds__(kBlock) void k_step(int8_t *boards, int64_t n, int6
         // rows -> line form of the action and back through the LDS selector table (k_step_n's
         // orientation machinery with o = rows on entry and exit)
         uint32_t obe = 0, obo = 0;
-        LaneOut re = step_lane_lines<RANDOM, AUTO_RESET, REWARD>(be, obe, tab, ae, de, want_score);
-        LaneOut ro = step_lane_lines<RANDOM, AUTO_RESET, REWARD>(bo, obo, tab, ao, dd, want_score);
+        LaneOut re = step_lane_lines<RANDOM, AUTO_RESET, REWARD, false>(be, obe, tab, nullptr, ae, de, want_score);
+        LaneOut ro = step_lane_lines<RANDOM, AUTO_RESET, REWARD, false>(bo, obo, tab, nullptr, ao, dd, want_score);
         re.b = r48::reorient(be, orient_at(tab, obe));
         ro.b = r48::reorient(bo, orient_at(tab, obo));
         emit_pair<RANDOM, REWARD>(re, ro, i, boards, actions, done, changed, reward, score);
@@ -321,6 +346,12 @@ __global__ __launch_bounds__(kBlock) void k_step(int8_t *boards, int64_t n, int6
 // are overwritten by every step). Same draw contract as k_step, step counter step0 + t. Bound:
 // VALU issue (~200 VALU per board-step); HBM traffic is 34 B per board per
 // call, not per step.
+// LDS per block: the 256-byte selector table and, under AUTO_RESET, the 2 KiB table of reset
+// boards in line form (threads 0..127 compute one entry each at kernel start; 8 resident blocks
+// per CU hold 18 KiB, occupancy stays at 8 waves per SIMD). A finished board is reset inside the
+// wave-uniform `any done` branch by one ds_read_b128 + four selects and stays in the line form of
+// the step's action like every other board, so after the loop every board returns to rows from
+// the line form of its last action.
 // TRAJ (r48_env_rollout): also every step's action and done into row t of traj_actions /
 // traj_done ([n_steps][n], each nullable) -- one 2-byte store per plane per pair and step.
 template <bool RANDOM, bool AUTO_RESET, bool REWARD, int NP, bool TRAJ = false>
@@ -339,7 +370,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(REWARD ?
     const bool want_score = score != nullptr;
     const int32_t last = n_steps - 1;
     __shared__ __attribute__((aligned(16))) r48::Orient tab[16];
-    load_orient_table(tab);
+    // the reset boards in line form (2 KiB; no LDS without AUTO_RESET: the array is never touched)
+    __shared__ __attribute__((aligned(16))) Board rtab[AUTO_RESET ? kResetEntries : 1];
+    static_assert(kBlock >= kResetEntries, "one thread per reset-table entry");
+    load_orient_table<AUTO_RESET>(tab, rtab);
     // trajectory rows whose pair addresses are not all 2-byte aligned (odd n or odd row pointers)
     // take byte stores inside the fast path, instead of sending the whole grid down the guarded one
     const bool traj_bytes = TRAJ && ((n | (int64_t)((uintptr_t)traj_actions | (uintptr_t)traj_done)) & 1) != 0;
@@ -396,6 +430,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(REWARD ?
             sd[j] = orient_at(tab, (dd[j].x >> 26) & 0x30u);
         }
         int32_t t = 0;
+#if R48_STEPN_LOOP_PAD
+        // Code placement: each s_nop here, executed once per call, moves the
+        // step loop by 4 bytes. A scan of all 16 placements mod 64 of this loop
+        // (profiles/r06/env/stepn_reset_table_ab.txt) splits cleanly in two: loop start = 4 mod 8
+        // runs 3.23-3.27 us per 2^20-board step, 0 mod 8 runs 3.35-3.38. Unpadded, the random-policy
+        // auto-reset loop starts at 0x20 mod 64; one s_nop puts it at 0x24, where the loop before the
+        // table reset already sat. Any edit that changes the code size before the loop needs the scan again.
+        asm volatile(".rept %0\n\ts_nop 0\n\t.endr" ::"n"(R48_STEPN_LOOP_PAD));
+#endif
 #pragma nounroll
         for (int ph = 0; ph < 4; ph++) {
             switch (ph) {   // s_setprio takes an immediate
@@ -413,20 +456,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(REWARD ?
                     pair_draws(q[j], step + 1u, k0, k1, ne, nd);
                     if (RANDOM) {
                         const uint32_t ane = (ne.x >> 26) & 0x30u, and_ = (nd.x >> 26) & 0x30u;
-                        // this step's reorient first, then the next step's selector reads into the
-                        // same registers: their LDS latency runs under this step's move
-                        r48::Orient xe = orient_at(tab, ((de[j].x >> 24) & 0xC0u) + ane);
-                        r48::Orient xd = orient_at(tab, ((dd[j].x >> 24) & 0xC0u) + and_);
+                        // the next step's selector reads first (their LDS latency runs under this
+                        // step's move); a reset leaves them as they are: the board keeps its line form
+                        const r48::Orient xe = orient_at(tab, ((de[j].x >> 24) & 0xC0u) + ane);
+                        const r48::Orient xd = orient_at(tab, ((dd[j].x >> 24) & 0xC0u) + and_);
                         b[2 * j] = r48::reorient(b[2 * j], se[j]);
                         b[2 * j + 1] = r48::reorient(b[2 * j + 1], sd[j]);
-                        r[2 * j] = step_lane_pre<AUTO_RESET, REWARD>(b[2 * j], xe, ane, tab, de[j], sc);
-                        r[2 * j + 1] = step_lane_pre<AUTO_RESET, REWARD>(b[2 * j + 1], xd, and_, tab, dd[j], sc);
+                        r[2 * j] = step_lane_pre<AUTO_RESET, REWARD>(b[2 * j], rtab, de[j], sc);
+                        r[2 * j + 1] = step_lane_pre<AUTO_RESET, REWARD>(b[2 * j + 1], rtab, dd[j], sc);
                         se[j] = xe;
                         sd[j] = xd;
                     } else {
-                        r[2 * j] = step_lane_lines<RANDOM, AUTO_RESET, REWARD>(b[2 * j], ob[2 * j], tab, a[2 * j], de[j], sc);
-                        r[2 * j + 1] = step_lane_lines<RANDOM, AUTO_RESET, REWARD>(b[2 * j + 1], ob[2 * j + 1], tab,
-                                                                                   a[2 * j + 1], dd[j], sc);
+                        r[2 * j] = step_lane_lines<RANDOM, AUTO_RESET, REWARD, AUTO_RESET>(b[2 * j], ob[2 * j], tab, rtab,
+                                                                                           a[2 * j], de[j], sc);
+                        r[2 * j + 1] = step_lane_lines<RANDOM, AUTO_RESET, REWARD, AUTO_RESET>(
+                            b[2 * j + 1], ob[2 * j + 1], tab, rtab, a[2 * j + 1], dd[j], sc);
                     }
                     de[j] = ne;
                     dd[j] = nd;
@@ -453,11 +497,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(REWARD ?
                 }
             }
         }
-        if (RANDOM) {   // the line form of the last action, or rows after a reset in the last step
-            // (without AUTO_RESET a done board is not reset: it stays in the line form of its action)
+        if (RANDOM) {   // the line form of the last action, reset or not (a reset board is reset in that form)
 #pragma unroll
             for (int j = 0; j < 2 * NP; j++)
-                ob[j] = (AUTO_RESET && r[j].done) ? 0u : r[j].a << 6;
+                ob[j] = r[j].a << 6;
         }
 #pragma unroll
         for (int j = 0; j < NP; j++) {
