@@ -643,6 +643,20 @@ int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int
                       const float *tables, int32_t depth, int8_t *actions, float *q, uint8_t *legal,
                       void *stream);
 
+/* The same search three plies deep, one kernel, one board per workgroup. With best_k(board) = the
+ * largest Q_k over the board's legal moves and 0 where it has none, Q_1 = depth 1's Q, and for
+ * k >= 2
+ *   Q_k(a) = (float)r_a + S_a / (float)(10 |E|), S_a = the sum over the sixteen cells c of
+ *            fmaf(9, best_(k-1)(s_a[c <- 1]), best_(k-1)(s_a[c <- 2])), +0 for a cell that holds a tile,
+ * this writes Q_3: a depth-2 search of each of the board's 2 to 120 children after a move and a
+ * spawn, then depth 2's averaging step. Outputs, the -inf of illegal moves, the first-maximiser
+ * action and the fixed tree order of S_a at both levels are r48_ntuple_search's: q is bitwise
+ * reproducible and does not depend on the board's place in the batch. R48_EINVAL as above, and
+ * for NULL tables or actions, tables or q not 4-byte aligned, or n beyond 2^31 - 1 boards (the
+ * grid). r48_ntuple_search itself keeps refusing depth 3. */
+int r48_ntuple_search3(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                       const float *tables, int8_t *actions, float *q, uint8_t *legal, void *stream);
+
 /* The TD update in two launches, both over the hits (i, t, g) of the boards with valid[i] != 0
  * (valid NULL: all). Scratch: acc int64[m][16^L], cnt uint32[m][16^L], which MUST BE ALL ZERO ON
  * ENTRY to r48_ntuple_accumulate (r48_ntuple_apply leaves them zero again).

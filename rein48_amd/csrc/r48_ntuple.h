@@ -17,7 +17,7 @@
 // Summation order (the contract every kernel here shares, so value and act agree bit for bit):
 // fp32, starting from 0, hits in the order p = 8t + g = 0, 1, ..., 8m - 1.
 //
-// The search (k_nt_search, and nt_search_board for one board on the host). For a move a that
+// The search (k_nt_search, k_nt_search3, and nt_search_board for one board on the host). For a move a that
 // changes the board: afterstate s_a, merge reward r_a, and
 //     depth 1   Q(a) = (float)r_a + V(s_a)                                  (act's score)
 //     depth 2   Q(a) = (float)r_a + S_a / (float)(10 |E|),  E = the empty cells of s_a,
@@ -36,6 +36,16 @@
 //     (((x0 + x1) + (x2 + x3)) + ((x4 + x5) + (x6 + x7))) + (the same of x8 .. x15). fp32 addition
 //     commutes, so every lane of the butterfly holds these bits. The order depends on nothing
 //     but the cell numbers: not on the batch, on n, or on which cells are empty.
+//
+// The same, recursively, for any number of plies k (k_nt_search3 runs k = 3, nt_search_board 1..3):
+//     best_k(board) = max over the board's legal moves a of Q_k(a), 0 where it has none
+//     Q_1(a)        = (float)r_a + V(s_a)
+//     Q_k(a), k > 1 = (float)r_a + S_a / (float)(10 |E|),  S_a = nt_sum16 of the sixteen cell terms
+//                     x_c = fmaf(9, best_(k-1)(s_a[c <- 1]), best_(k-1)(s_a[c <- 2])), x_c = +0 where
+//                     cell c of s_a holds a tile
+// Depth 2 is the above with leaf = best_1; depth 3's leaf is best_2. The arithmetic is the same at
+// every level: fp32, nt_fma for a cell term, the butterfly's order, one division by 10 |E| per
+// level (nt_q2). The max over the legal moves of fp32 scores does not depend on their order.
 #pragma once
 #include <stdint.h>
 
@@ -376,9 +386,52 @@ inline float nt_sum16(const float *x)
     return v[0];
 }
 
-// The whole search of one board, serially: the host's restatement of k_nt_search, which runs the
-// same nt_leaf / nt_fma / nt_q2 / nt_argmax4 but spreads the children over the lanes of a wave
-// and sums with the butterfly. Returns the action; q[4] and legal as the kernel writes them.
+template <int L>
+inline float nt_q_level(const Board &s, uint32_t r, const NtLayout &lay, const float *tables, int k);
+
+// best_k(board) of the contract, on the host: plain recursion. best_1 is nt_leaf.
+template <int L>
+inline float nt_best(const Board &board, const NtLayout &lay, const float *tables, int k)
+{
+    if (k <= 1)
+        return nt_leaf<L>(board, lay, tables);
+    const Moves4 m = move_rows4<true>(board);
+    const uint32_t lg = nt_legal4(m, board);
+    float best = 0.0f;
+    bool have = false;
+    for (uint32_t a = 0; a < 4u; a++) {
+        if (!((lg >> a) & 1u))
+            continue;
+        const float s = nt_q_level<L>(nt_pick(m, a), nt_pick_reward(m, a), lay, tables, k);
+        if (!have || s > best) {
+            have = true;
+            best = s;
+        }
+    }
+    return best;
+}
+
+// Q_k(a), k >= 2, from the move's afterstate s and reward r
+template <int L>
+inline float nt_q_level(const Board &s, uint32_t r, const NtLayout &lay, const float *tables, int k)
+{
+    float x[16];
+    for (uint32_t c = 0; c < 16u; c++) {
+        x[c] = 0.0f;
+        if (nt_cell(s, c) != 0u)
+            continue;
+        Board two = s, four = s;
+        place(two, c, 1u, true);
+        place(four, c, 2u, true);
+        x[c] = nt_fma(9.0f, nt_best<L>(two, lay, tables, k - 1), nt_best<L>(four, lay, tables, k - 1));
+    }
+    return nt_q2(r, nt_sum16(x), blanks(s).n);
+}
+
+// The whole search of one board, serially, at depth 1, 2 or 3: the host's restatement of
+// k_nt_search and k_nt_search3, which run the same nt_leaf / nt_fma / nt_q2 / nt_argmax4 but
+// spread the children over lanes and waves and sum with the butterfly. Returns the action; q[4]
+// and legal as the kernels write them.
 template <int L>
 inline uint32_t nt_search_board(const Board &b, const NtLayout &lay, const float *tables, int depth, float q[4],
                                 uint32_t &legal)
@@ -395,10 +448,7 @@ inline uint32_t nt_search_board(const Board &b, const NtLayout &lay, const float
             q[a] = nt_score<L>(s, r, lay, tables);
             continue;
         }
-        float x[16];
-        for (uint32_t c = 0; c < 16u; c++)
-            x[c] = nt_cell_term<L>(s, c, lay, tables);
-        q[a] = nt_q2(r, nt_sum16(x), blanks(s).n);
+        q[a] = nt_q_level<L>(s, r, lay, tables, depth);
     }
     return nt_argmax4(q[0], q[1], q[2], q[3]);
 }

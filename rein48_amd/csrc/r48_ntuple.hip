@@ -17,6 +17,8 @@
 //   k_nt_tc_rate     board -> the mean learning rate |E| / A over its 8m hits (read-only)
 //   k_nt_search      board -> the four action values Q and their first argmax at depth 1 (act's
 //                    scores) or depth 2 (expectimax over the tile spawn); one board per WAVE
+//   k_nt_search3     the same three plies deep: one board per WORKGROUP, whose waves search the
+//                    board's children with depth 2's wave-level routine
 // Otherwise one board per lane, one 16-byte board load; templated on the tuple length L so the cell loops
 // unroll; the expanded layout travels by value in the kernel arguments (wave-uniform).
 #include <hip/hip_runtime.h>
@@ -229,6 +231,49 @@ __global__ __launch_bounds__(kBlock) void k_nt_tc_rate(const int8_t *__restrict_
 // read from lanes 0, 16, 32, 48; those lanes write q, lane 0 the action and the legal set.
 constexpr int kSearchBoards = kBlock / 64;   // boards (waves) per workgroup
 
+// The depth-2 search of a board that every lane of the wave holds (the comment above): the
+// lane's Q_2 of its row's move (-inf where the move is illegal) and the board's legal set. Shared
+// by k_nt_search<L, 2>, whose board is the batch's, and k_nt_search3, whose boards are the root's
+// children.
+template <int L>
+__device__ __forceinline__ float nt_wave_q2(const r48::Board &b, uint32_t lane, const r48::NtLayout &lay,
+                                            const float *__restrict__ tables, uint32_t &lg)
+{
+    const uint32_t a = lane >> 4, c = lane & 15u;
+    const r48::Moves4 m = r48::move_rows4<true>(b);
+    lg = r48::nt_legal4(m, b);
+    const r48::Board s = r48::nt_pick(m, a);
+    const uint32_t r = r48::nt_pick_reward(m, a);
+    const bool ok = ((lg >> a) & 1u) != 0u;
+    const bool slot = ok && r48::nt_cell(s, c) == 0u;
+    const uint64_t M = __ballot(slot);
+    const uint32_t kids = 2u * (uint32_t)__popcll(M);
+    const uint32_t rank2 = 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
+    float leaf0 = 0.0f, leaf1 = 0.0f;
+#pragma unroll 1
+    for (uint32_t base = 0u; base < kids; base += 64u) {   // uniform: at most two rounds
+        float leaf = 0.0f;
+        if (base + lane < kids) {
+            const uint32_t p = r48::nt_select_bit(M, (base + lane) >> 1);
+            r48::Board child = r48::nt_pick(m, p >> 4);
+            r48::place(child, p & 15u, 1u + (lane & 1u), true);
+            leaf = r48::nt_leaf<L>(child, lay, tables);
+        }
+        leaf0 = base == 0u ? leaf : leaf0;
+        leaf1 = base == 0u ? leaf1 : leaf;
+    }
+    const int src = (int)(rank2 & 63u);
+    const float two0 = __shfl(leaf0, src), four0 = __shfl(leaf0, src + 1);
+    const float two1 = __shfl(leaf1, src), four1 = __shfl(leaf1, src + 1);
+    const bool late = rank2 >= 64u;
+    float x = slot ? r48::nt_fma(9.0f, late ? two1 : two0, late ? four1 : four0) : 0.0f;
+    x += __shfl_xor(x, 1);
+    x += __shfl_xor(x, 2);
+    x += __shfl_xor(x, 4);
+    x += __shfl_xor(x, 8);
+    return ok ? r48::nt_q2(r, x, r48::blanks(s).n) : -__builtin_inff();
+}
+
 template <int L, int DEPTH>
 __global__ __launch_bounds__(kBlock) void k_nt_search(const int8_t *__restrict__ boards, int64_t n,
                                                       const r48::NtLayout lay, const float *__restrict__ tables,
@@ -241,47 +286,155 @@ __global__ __launch_bounds__(kBlock) void k_nt_search(const int8_t *__restrict__
         return;   // the whole wave
     const uint32_t lane = threadIdx.x & 63u, a = lane >> 4, c = lane & 15u;
     const r48::Board b = r48::load_board(boards, i);
-    const r48::Moves4 m = r48::move_rows4<true>(b);
-    const uint32_t lg = r48::nt_legal4(m, b);
-    const r48::Board s = r48::nt_pick(m, a);
-    const uint32_t r = r48::nt_pick_reward(m, a);
-    const bool ok = ((lg >> a) & 1u) != 0u;
+    uint32_t lg;
     float qa;
     if (DEPTH == 1) {
+        const r48::Moves4 m = r48::move_rows4<true>(b);
+        lg = r48::nt_legal4(m, b);
+        const bool ok = ((lg >> a) & 1u) != 0u;
         float x = 0.0f;
         if (ok && c == 0u)
-            x = r48::nt_score<L>(s, r, lay, tables);
-        qa = __shfl(x, (int)(lane & 48u));
+            x = r48::nt_score<L>(r48::nt_pick(m, a), r48::nt_pick_reward(m, a), lay, tables);
+        qa = ok ? __shfl(x, (int)(lane & 48u)) : -__builtin_inff();
     } else {
-        const bool slot = ok && r48::nt_cell(s, c) == 0u;
-        const uint64_t M = __ballot(slot);
-        const uint32_t kids = 2u * (uint32_t)__popcll(M);
-        const uint32_t rank2 = 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
-        float leaf0 = 0.0f, leaf1 = 0.0f;
-#pragma unroll 1
-        for (uint32_t base = 0u; base < kids; base += 64u) {   // uniform: at most two rounds
-            float leaf = 0.0f;
-            if (base + lane < kids) {
-                const uint32_t p = r48::nt_select_bit(M, (base + lane) >> 1);
-                r48::Board child = r48::nt_pick(m, p >> 4);
-                r48::place(child, p & 15u, 1u + (lane & 1u), true);
-                leaf = r48::nt_leaf<L>(child, lay, tables);
-            }
-            leaf0 = base == 0u ? leaf : leaf0;
-            leaf1 = base == 0u ? leaf1 : leaf;
-        }
-        const int src = (int)(rank2 & 63u);
-        const float two0 = __shfl(leaf0, src), four0 = __shfl(leaf0, src + 1);
-        const float two1 = __shfl(leaf1, src), four1 = __shfl(leaf1, src + 1);
-        const bool late = rank2 >= 64u;
-        float x = slot ? r48::nt_fma(9.0f, late ? two1 : two0, late ? four1 : four0) : 0.0f;
-        x += __shfl_xor(x, 1);
-        x += __shfl_xor(x, 2);
-        x += __shfl_xor(x, 4);
-        x += __shfl_xor(x, 8);
-        qa = r48::nt_q2(r, x, r48::blanks(s).n);
+        qa = nt_wave_q2<L>(b, lane, lay, tables, lg);
     }
-    qa = ok ? qa : -__builtin_inff();
+    const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
+    if (q && c == 0u)
+        q[4 * i + a] = qa;
+    if (lane == 0u) {
+        actions[i] = (int8_t)r48::nt_argmax4(q0, q1, q2, q3);
+        if (legal)
+            legal[i] = (uint8_t)lg;
+    }
+}
+
+// The 3-ply search of r48_ntuple.h: a depth-2 search (nt_wave_q2) of each of the root's 2 to 120
+// children, then the averaging step depth 2 ends with. One board per workgroup of WAVES waves.
+// Wave 0 loads the board, makes the four moves and forms the root's slot ballot M with
+// lane = 16 a + c as depth 2 does, and leaves the four afterstates, their rewards, the legal set
+// and M in LDS; after the one barrier every wave reads what it needs from there (the other waves
+// make no root move at all). The root's child j is spawn 1 + (j & 1) in the slot
+// nt_select_bit(M, j >> 1), wave-uniform. The children are dealt through an LDS counter: wave w
+// starts with child w and takes the next undealt one after each. A wave searches its child and
+// its lane 0 stores best_2(child) = the largest of the child's four Q_2, 0 where it has no move,
+// to leaf[j]. A wave that finds no child left adds the number it did to a second counter and
+// leaves; the wave whose addition completes the count -- the last to arrive, whichever it is --
+// finishes as depth 2 does: the slot lane of rank rho reads leaf[2 rho] and leaf[2 rho + 1],
+// forms x_c by nt_fma, the butterfly and nt_q2 follow. Nobody waits for the slowest child. A leaf
+// is the same wave-level routine on the same child and the last step reads leaves by child
+// number, so where a board is in the grid, how the children were dealt and which wave did what
+// do not reach the bits. A board with no legal move has no child: the workgroup leaves right
+// after the barrier.
+// How many waves share a board trades latency against throughput (DESIGN.md has the A/B): with 16
+// a board's ~35 children are done in 2 to 3 rounds, which is the time of a small batch; in a
+// large batch the machine is full either way, what counts is how many waves are resident, and a
+// workgroup of 4 waves fills the wave slots that one of 16 leaves empty while its last children
+// finish. The bits do not depend on it. R48_NT_SEARCH3_WAVES (an experiment's build) fixes one
+// number for every n.
+#ifdef R48_NT_SEARCH3_WAVES
+constexpr int kSearch3WavesSmall = R48_NT_SEARCH3_WAVES, kSearch3WavesLarge = R48_NT_SEARCH3_WAVES;
+#else
+constexpr int kSearch3WavesSmall = 16, kSearch3WavesLarge = 4;
+#endif
+constexpr int64_t kSearch3SmallBatch = 8192;   // boards up to which the small batch's mapping runs
+constexpr int kSearch3MaxKids = 120;           // 2 spawns in at most 4 * 15 slots
+
+__device__ __forceinline__ uint32_t uniform_word(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+
+// what wave 0 leaves for the others
+struct Search3Root {
+    uint32_t after[4][4];   // the afterstate of move a, words w0 .. w3
+    uint32_t reward[4];
+    uint32_t legal, slots_lo, slots_hi;
+    uint32_t dealt, done;   // children handed out; children whose leaf is stored
+};
+
+template <int L, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restrict__ boards, int64_t n,
+                                                           const r48::NtLayout lay, const float *__restrict__ tables,
+                                                           int8_t *__restrict__ actions, float *__restrict__ q,
+                                                           uint8_t *__restrict__ legal)
+{
+    static_assert(WAVES >= 1 && WAVES <= 16, "a workgroup has at most 1024 lanes");
+    __shared__ float leaf[kSearch3MaxKids];
+    __shared__ Search3Root root;
+    const int64_t i = blockIdx.x;   // the grid has one workgroup per board
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u, a = lane >> 4, c = lane & 15u;
+    if (w == 0u) {
+        const r48::Board b = r48::load_board(boards, i);
+        const r48::Moves4 m = r48::move_rows4<true>(b);
+        const uint32_t lg = r48::nt_legal4(m, b);
+        const r48::Board s = r48::nt_pick(m, a);
+        const uint64_t M = __ballot(((lg >> a) & 1u) != 0u && r48::nt_cell(s, c) == 0u);
+        if (c == 0u) {
+            root.after[a][0] = s.w0;
+            root.after[a][1] = s.w1;
+            root.after[a][2] = s.w2;
+            root.after[a][3] = s.w3;
+            root.reward[a] = r48::nt_pick_reward(m, a);
+        }
+        if (lane == 0u) {
+            root.legal = lg;
+            root.slots_lo = (uint32_t)M;
+            root.slots_hi = (uint32_t)(M >> 32);
+            root.dealt = (uint32_t)WAVES;   // children 0 .. waves - 1 are dealt by wave number
+            root.done = 0u;
+        }
+    }
+    __syncthreads();
+    const uint32_t lg = uniform_word(root.legal);
+    if (lg == 0u) {   // uniform over the workgroup
+        if (w == 0u && lane == 0u) {
+            actions[i] = 0;
+            if (legal)
+                legal[i] = 0;
+        }
+        if (q && w == 0u && c == 0u)
+            q[4 * i + a] = -__builtin_inff();
+        return;
+    }
+    const uint64_t M = (uint64_t)uniform_word(root.slots_lo) | ((uint64_t)uniform_word(root.slots_hi) << 32);
+    const uint32_t kids = 2u * (uint32_t)__popcll(M);   // 4 .. 120
+    uint32_t mine = 0u;
+#pragma unroll 1
+    for (uint32_t j = w; j < kids; mine++) {
+        const uint32_t p = r48::nt_select_bit(M, j >> 1);   // < 64
+        const uint32_t *sa = root.after[p >> 4];
+        r48::Board child{sa[0], sa[1], sa[2], sa[3]};
+        r48::place(child, p & 15u, 1u + (j & 1u), true);
+        uint32_t lg2;
+        const float q2a = nt_wave_q2<L>(child, lane, lay, tables, lg2);
+        // the rows' scores; an illegal reply holds -inf, so the plain max is the max over the legal ones
+        const float b0 = __shfl(q2a, 0), b1 = __shfl(q2a, 16), b2 = __shfl(q2a, 32), b3 = __shfl(q2a, 48);
+        uint32_t next = 0u;
+        if (lane == 0u) {
+            leaf[j] = lg2 ? fmaxf(fmaxf(b0, b1), fmaxf(b2, b3)) : 0.0f;
+            next = __hip_atomic_fetch_add(&root.dealt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        j = uniform_word(next);
+    }
+    if (mine == 0u)
+        return;   // more waves than children
+    uint32_t before = 0u;
+    if (lane == 0u)   // releases this wave's leaves, acquires the others' where it completes the count
+        before = __hip_atomic_fetch_add(&root.done, mine, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (uniform_word(before) + mine != kids)
+        return;
+    const r48::Board s{root.after[a][0], root.after[a][1], root.after[a][2], root.after[a][3]};
+    const uint32_t r = root.reward[a];
+    const bool ok = ((lg >> a) & 1u) != 0u;
+    const bool slot = ((M >> lane) & 1ull) != 0ull;
+    const uint32_t rank2 = 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
+    float x = 0.0f;
+    if (slot)   // rank2 + 1 < kids <= 120
+        x = r48::nt_fma(9.0f, leaf[rank2], leaf[rank2 + 1u]);
+    x += __shfl_xor(x, 1);
+    x += __shfl_xor(x, 2);
+    x += __shfl_xor(x, 4);
+    x += __shfl_xor(x, 8);
+    const float qa = ok ? r48::nt_q2(r, x, r48::blanks(s).n) : -__builtin_inff();
     const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
     if (q && c == 0u)
         q[4 * i + a] = qa;
@@ -379,6 +532,42 @@ int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int
     }
 #undef R48_NT_SEARCH
     return launched("k_nt_search");
+}
+
+int r48_ntuple_search3(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                       const float *tables, int8_t *actions, float *q, uint8_t *legal, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_common("r48_ntuple_search3", boards, n, cells, m, L, lay))
+        return rc;
+    if (!tables || !actions || !aligned(tables, 4) || !aligned(q, 4))
+        return fail(R48_EINVAL, "r48_ntuple_search3: tables/actions NULL, or tables / q not 4-byte aligned");
+    if (n > 0x7FFFFFFFll)   // one board per workgroup
+        return fail(R48_EINVAL, "r48_ntuple_search3: n = " + std::to_string(n) +
+                                    " boards exceed the grid (one per workgroup, 2^31 - 1 workgroups)");
+    if (n == 0)
+        return R48_OK;
+    const dim3 grid((unsigned)n);
+    const hipStream_t st = (hipStream_t)stream;
+    const bool small = n <= kSearch3SmallBatch;
+#define R48_NT_SEARCH3(LEN)                                                                                          \
+    case LEN:                                                                                                        \
+        if (small)                                                                                                   \
+            hipLaunchKernelGGL((k_nt_search3<LEN, kSearch3WavesSmall>), grid, dim3(64 * kSearch3WavesSmall), 0, st,  \
+                               boards, n, lay, tables, actions, q, legal);                                           \
+        else                                                                                                         \
+            hipLaunchKernelGGL((k_nt_search3<LEN, kSearch3WavesLarge>), grid, dim3(64 * kSearch3WavesLarge), 0, st,  \
+                               boards, n, lay, tables, actions, q, legal);                                           \
+        break;
+    switch (lay.L) {
+        R48_NT_SEARCH3(2)
+        R48_NT_SEARCH3(3)
+        R48_NT_SEARCH3(4)
+        R48_NT_SEARCH3(5)
+        R48_NT_SEARCH3(6)
+    }
+#undef R48_NT_SEARCH3
+    return launched("k_nt_search3");
 }
 
 int r48_ntuple_accumulate(const int8_t *boards, int64_t n, const float *delta, const uint8_t *valid,

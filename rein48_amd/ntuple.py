@@ -145,7 +145,7 @@ class NTupleNet:
         score on the board after the spawn, 0 where that board has no move. Illegal moves have q =
         -inf; the action is the first maximiser, 0 where no move is legal. One board per wave."""
         if depth not in (1, 2):
-            raise ValueError("search depth is 1 or 2, got %r" % (depth,))
+            raise ValueError("search depth is 1 or 2, got %r (three plies: search3)" % (depth,))
         n = _boards(boards)
         actions = _out(actions, "actions", torch.int8, (n,), boards)
         q = _out(q, "q", torch.float32, (n, 4), boards)
@@ -154,17 +154,35 @@ class NTupleNet:
                                           ptr(legal), _stream(boards)))
         return actions, q, legal
 
+    def search3(self, boards, actions=None, q=None, legal=None):
+        """The 3-ply expectimax search -> (actions int8 [n], q float32 [n, 4], legal uint8 [n]):
+        search's depth 2 with the leaf one level deeper. q[a] = reward + the mean over the tile
+        spawns of the best depth-2 q on the board after the spawn, 0 where that board has no move.
+        Illegal moves, the action and the summation order are search's; q is bitwise reproducible.
+        One kernel, one board per workgroup: a depth-2 search of each of the board's 2 to 120
+        children."""
+        n = _boards(boards)
+        actions = _out(actions, "actions", torch.int8, (n,), boards)
+        q = _out(q, "q", torch.float32, (n, 4), boards)
+        legal = _out(legal, "legal", torch.uint8, (n,), boards)
+        check(self._lib.r48_ntuple_search3(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(actions), ptr(q),
+                                           ptr(legal), _stream(boards)))
+        return actions, q, legal
+
     def policy(self, depth=1):
         """`policy(boards, t) -> actions` for evaluate.play_episodes: the fused greedy search (depth
-        1, act) or the 2-ply expectimax search (depth 2)."""
-        if depth not in (1, 2):
-            raise ValueError("policy depth is 1 or 2, got %r" % (depth,))
+        1, act), the 2-ply expectimax search (depth 2) or the 3-ply one (depth 3, search3)."""
+        if depth not in (1, 2, 3):
+            raise ValueError("policy depth is 1, 2 or 3, got %r" % (depth,))
         if depth == 1:
             def policy(boards, t):
                 return self.act(boards.contiguous())[0]
-        else:
+        elif depth == 2:
             def policy(boards, t):
                 return self.search(boards.contiguous(), 2)[0]
+        else:
+            def policy(boards, t):
+                return self.search3(boards.contiguous())[0]
         return policy
 
     def state_dict(self):

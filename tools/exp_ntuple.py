@@ -3,6 +3,7 @@
     python tools/exp_ntuple.py [--out DIR] [--sizes 65536,1048576] [--scores]
     python tools/exp_ntuple.py --search [--out DIR] [--sizes 4096,65536] [--scores] [--long]
     python tools/exp_ntuple.py --tc [--out DIR] [--sizes 65536,1048576] [--scores]
+    python tools/exp_ntuple.py --search3 [--out DIR] [--sizes 256,4096,16384] [--scores] [--episodes N] [--ab-lib SO]
 
 For both named layouts and each board count: device-event times (5 warm-up calls, median of 7
 windows of 20 calls) of value, act, accumulate and apply with their table loads or atomics per
@@ -23,6 +24,17 @@ every legal afterstate laid out by torch -> act on the children -> torch reducti
 (c) picks the fused search's action. With --scores: whole-episode scores of policy(depth=1) against
 policy(depth=2) on the same trained tables (1,024 x 2,000 steps for both layouts; --long adds 4,096 x
 10,000 for 4x6), 4,096 episodes, eval seed 13. Writes exp_ntuple_search.json under --out.
+
+--search3: the 3-ply search. For both layouts and each board count (default 256, 4,096 and 2^14), the
+same device-event method with alternated windows on (a) search3, (b) search(depth=2) and (c) the
+unfused composition written here (unfused_search with the depth-2 kernel for the leaves: afterstates
+-> the root's children laid out by torch, a host sync -> search(children, 2) -> torch max, scatter-add
+and argmax), with the share of boards on which (c) picks search3's action. --ab-lib SO[,SO...]: other
+builds of the library (-DR48_NT_SEARCH3_WAVES=4, 16, ...: the waves that share a board) whose
+r48_ntuple_search3 are alternated with this one's in the same windows, outputs compared bit for bit. With --scores: play_episodes at depths
+2 and 3 with the recorded recipes' tables (lines-squares and 4x6 at 1,024 x 2,000 steps TD(0), 4x6 at
+4,096 x 10,000 TC; --episodes each, default 4,096, eval seed 13) and the learning test's recipe
+(lines-squares 1,024 x 1,000, 512 episodes, eval seed 1). Writes exp_ntuple_search3.json.
 
 --tc: temporal-coherence learning rates against plain TD(0). For both layouts and each board count,
 device-event times in one process with alternated windows (TD window, TC window, TD window, ...;
@@ -141,8 +153,9 @@ def scores(layout, n_boards, steps, eval_seed=13):
             "eval_seed": eval_seed, "eval": ev}
 
 
-def unfused_search(net):
-    """The depth-2 search composed from the entry points that existed before it: one afterstates
+def unfused_search(net, leaves=None):
+    """leaves(kids) -> float32 [K]: the value of every child; the default is depth 2's, act's best
+    score. The depth-2 search composed from the entry points that existed before it: one afterstates
     launch, the children of every legal afterstate (each empty cell filled with a 2 and with a 4)
     gathered by torch, act on the children for their leaves, a torch scatter-add for S_a and the
     argmax. Returns (actions, q [4, n]). The scatter-add uses float atomics, so q is not
@@ -161,8 +174,11 @@ def unfused_search(net):
         kids = after[ia, ii].repeat_interleave(2, dim=0)                # [2k, 16]: e = 1, 2 per cell
         e = torch.tensor([1, 2], dtype=torch.int8, device=DEV).repeat(k)
         kids[torch.arange(2 * k, device=DEV), ic.repeat_interleave(2)] = e
-        _, _, v, r, lg = net.act(kids)
-        leaf = torch.where(lg != 0, r.float() + v, torch.zeros_like(v))
+        if leaves is None:
+            _, _, v, r, lg = net.act(kids)
+            leaf = torch.where(lg != 0, r.float() + v, torch.zeros_like(v))
+        else:
+            leaf = leaves(kids)
         w = torch.tensor([9.0, 1.0], device=DEV).repeat(k)
         s = torch.zeros((4, n), dtype=torch.float32, device=DEV)
         s.index_put_((ia.repeat_interleave(2), ii.repeat_interleave(2)), w * leaf, accumulate=True)
@@ -363,6 +379,119 @@ def main_tc(args):
             json.dump(out, f, indent=1)
 
 
+def running_boards(n):
+    env = VecGame(n, device=DEV, seed=7)
+    env.reset()
+    greedy = afterstate_policy(None)
+    for t in range(150):
+        env.step(greedy(env.boards, t), auto_reset=True)
+    return env.boards.clone()
+
+
+def search3_of_library(path, net):
+    """r48_ntuple_search3 of another build of the library, on net's tables."""
+    import ctypes as C
+    from rein48_amd import _lib
+    f = C.CDLL(path).r48_ntuple_search3
+    f.restype, f.argtypes = _lib.SIGNATURES["r48_ntuple_search3"]
+
+    def search3(boards, actions, q, legal):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(f(_lib.ptr(boards), boards.shape[0], *net._lay(), _lib.ptr(net.tables), _lib.ptr(actions), _lib.ptr(q),
+                     _lib.ptr(legal), stream))
+    return search3
+
+
+def search3_kernels(layout, n, ab_lib=None):
+    net = NTupleNet(layout, device=DEV)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    net.tables.copy_(torch.randn(net.tables.shape, generator=g, device=DEV) * 30.0)
+    boards = running_boards(n)
+    a, q, legal = net.search3(boards)
+    a2, q2, legal2 = net.search(boards, 2)
+
+    def leaves(kids):                                                   # best_2 of the root's children
+        _, qk, lg = net.search(kids, 2)
+        return torch.where(lg != 0, qk.max(dim=1).values, torch.zeros_like(qk[:, 0]))
+    unfused = unfused_search(net, leaves)
+    ua, uq = unfused(boards)
+    fin = torch.isfinite(q)
+    rel = ((uq.T[fin] - q[fin]).abs() / q[fin].abs().clamp(min=1.0)).max()
+    from rein48_amd.moves import afterstates
+    af, _, lg = afterstates(boards)
+    ok = ((lg.unsqueeze(0) >> torch.arange(4, device=DEV).view(4, 1)) & 1) != 0
+    children = 2 * int(((af == 0) & ok.unsqueeze(2)).sum())
+    res = {"layout": layout, "boards": n, "tuples": net.m, "length": net.L, "children": children,
+           "children_per_board": children / n, "unfused_actions_equal_fraction": float((ua == a).float().mean()),
+           "unfused_q_max_rel_diff": float(rel), "depth3_differs_from_depth2_fraction": float((a != a2).float().mean())}
+    fns = {"search3": lambda: net.search3(boards, a, q, legal), "search_depth2": lambda: net.search(boards, 2, a2, q2, legal2),
+           "search3_unfused": lambda: unfused(boards)}
+    for path in (ab_lib or "").split(","):
+        if not path:
+            continue
+        name = "search3_" + os.path.splitext(os.path.basename(path))[0]
+        other = search3_of_library(path, net)
+        ab, qb, lb = torch.empty_like(a), torch.empty_like(q), torch.empty_like(legal)
+        other(boards, ab, qb, lb)
+        res[name + "_bit_equal"] = bool(torch.equal(qb.view(torch.int32), q.view(torch.int32)) and torch.equal(ab, a) and
+                                        torch.equal(lb, legal))
+        fns[name] = lambda other=other, ab=ab, qb=qb, lb=lb: other(boards, ab, qb, lb)
+    for name, t in alternated_ms(fns).items():
+        res[name] = _ms(t)
+    res["search3"]["children_per_s"] = children / (res["search3"]["ms"] * 1e-3)
+    res["unfused_over_fused"] = res["search3_unfused"]["ms"] / res["search3"]["ms"]
+    res["search3_over_depth2"] = res["search3"]["ms"] / res["search_depth2"]["ms"]
+    del net
+    torch.cuda.empty_cache()
+    return res
+
+
+def search3_scores(layout, n_boards, steps, alpha=0.25, tc=False, eval_seed=13, episodes=4096):
+    tr = NTupleTrainer(NTupleConfig(n_boards=n_boards, layout=layout, alpha=alpha, seed=0, tc=tc), device=DEV)
+    for _ in range(steps):
+        tr.train_step()
+    torch.cuda.synchronize()
+    out = {"layout": layout, "train_boards": n_boards, "train_steps": steps, "alpha": alpha, "tc": tc,
+           "eval_seed": eval_seed, "episodes": episodes}
+    for depth in (2, 3):
+        t0 = time.perf_counter()
+        ev = play_episodes(tr.policy(depth=depth), episodes, device=DEV, seed=eval_seed, return_scores=True)
+        sc = ev.pop("scores").numpy()
+        ev["score_std"] = float(sc.std(ddof=1))
+        ev["standard_error"] = ev["score_std"] / episodes ** 0.5
+        ev["eval_seconds"] = time.perf_counter() - t0
+        out["depth%d" % depth] = ev
+    se = (out["depth2"]["standard_error"] ** 2 + out["depth3"]["standard_error"] ** 2) ** 0.5
+    out["difference_in_standard_errors"] = (out["depth3"]["mean_score"] - out["depth2"]["mean_score"]) / se
+    del tr
+    torch.cuda.empty_cache()
+    return out
+
+
+def main_search3(args):
+    out = {"device": torch.cuda.get_device_name(0), "ab_lib": args.ab_lib, "kernels": [], "scores": []}
+
+    def save():
+        if args.out:
+            os.makedirs(args.out, exist_ok=True)
+            with open(os.path.join(args.out, "exp_ntuple_search3.json"), "w") as f:
+                json.dump(out, f, indent=1)
+    for layout in ("lines-squares", "4x6"):
+        for n in (int(s) for s in (args.sizes or "256,4096,16384").split(",")):
+            r = search3_kernels(layout, n, args.ab_lib)
+            out["kernels"].append(r)
+            print(json.dumps(r), flush=True)
+    save()
+    if args.scores:
+        for layout, n_boards, steps, alpha, tc, seed, episodes in (
+                ("lines-squares", 1024, 1000, 0.25, False, 1, 512), ("lines-squares", 1024, 2000, 0.25, False, 13, args.episodes),
+                ("4x6", 1024, 2000, 0.25, False, 13, args.episodes), ("4x6", 4096, 10000, 1.0, True, 13, args.episodes)):
+            r = search3_scores(layout, n_boards, steps, alpha, tc, seed, episodes)
+            out["scores"].append(r)
+            print(json.dumps(r), flush=True)
+            save()
+
+
 def main_search(args):
     out = {"device": torch.cuda.get_device_name(0), "kernels": [], "scores": []}
     for layout in ("lines-squares", "4x6"):
@@ -390,9 +519,14 @@ def main():
     ap.add_argument("--search", action="store_true")
     ap.add_argument("--long", action="store_true")
     ap.add_argument("--tc", action="store_true")
+    ap.add_argument("--search3", action="store_true")
+    ap.add_argument("--episodes", type=int, default=4096)
+    ap.add_argument("--ab-lib", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("exp_ntuple.py needs a GPU")
+    if args.search3:
+        return main_search3(args)
     if args.search:
         return main_search(args)
     if args.tc:
