@@ -672,6 +672,27 @@ int r48_ntuple_accumulate(const int8_t *boards, int64_t n, const float *delta, c
 int r48_ntuple_apply(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
                      int32_t L, float step, float *tables, int64_t *acc, uint32_t *cnt, void *stream);
 
+/* The training step's first launch: r48_ntuple_act on the env boards and, in the same kernel, the
+ * TD error of every board and r48_ntuple_accumulate for the PREVIOUS step's afterstates.
+ *   actions, after, value, reward (nullable), legal: as r48_ntuple_act writes them, bit for bit
+ *   valid_out uint8[n] = legal != 0: this step's afterstate exists (the next call's prev_valid)
+ *   delta = (prev_done[i] ? 0.0f : (float)reward[i] + value[i]) - prev_value[i], fp32: the target is 0
+ *           where the previous step ended the episode. delta_out float[n] (nullable) receives it
+ *           for every board, prev_valid or not
+ *   where prev_valid[i] != 0: cnt[e] += 1, acc[e] += llrintf(clamp(delta, +-2^20) * 65536) over
+ *           the 8m hits e of prev_after[i] -- r48_ntuple_accumulate's words; acc and cnt must be
+ *           all zero on entry, r48_ntuple_apply / _apply_tc(prev_after, ..., prev_valid) follows
+ * tables is only read. Stateless: the caller keeps two sets of after / value / valid buffers and
+ * swaps them after apply. R48_EINVAL (before any HIP call) for the common cases, a NULL argument
+ * other than reward and delta_out, prev_after / after not 16-byte aligned, acc not 8-byte aligned,
+ * a float buffer, reward or cnt not 4-byte aligned, and after == prev_after, value == prev_value or
+ * valid_out == prev_valid. n == 0 is a no-op after the layout check. */
+int r48_ntuple_td_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                      const float *tables, const int8_t *prev_after, const float *prev_value,
+                      const uint8_t *prev_done, const uint8_t *prev_valid, int8_t *actions, int8_t *after,
+                      float *value, int32_t *reward, uint8_t *legal, uint8_t *valid_out, float *delta_out,
+                      int64_t *acc, uint32_t *cnt, void *stream);
+
 /* apply with temporal-coherence (TC) learning rates. tc_e and tc_a are float[m][16^L] like tables,
  * zero before the first update: E[e] is the running sum of the mean deltas entry e was updated
  * with, A[e] the running sum of their absolute values. For every entry hit, with mean =

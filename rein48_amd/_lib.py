@@ -135,6 +135,7 @@ SIGNATURES = {
     "r48_td_target_masked": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_float, _I32, _P, _P]),
     "r48_ntuple_value": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P]),
     "r48_ntuple_act": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "r48_ntuple_td_act": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "r48_ntuple_search": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
     "r48_ntuple_search3": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     "r48_ntuple_accumulate": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _I32, _P, _P, _P]),

@@ -214,6 +214,30 @@ R48_HD void nt_tc_update(float &table, float &e, float &a, float mean, float ste
     a += __builtin_fabsf(mean);
 }
 
+// ---- the TD step ------------------------------------------------------------------------------
+// The trainer's error for a board whose previous afterstate had value prev_value, from this step's
+// chosen move (merge reward, V of its afterstate): the target is 0 where the previous step ended
+// the episode (the board is a fresh game's), else (float)reward + value -- act's score.
+//     delta = target - prev_value
+// fp32: one conversion (exact, a reward is below 2^24), one addition, one subtraction; there is no
+// product, so nothing to contract.
+R48_HD float nt_td_delta(uint32_t prev_done, uint32_t reward, float value, float prev_value)
+{
+    return (prev_done ? 0.0f : (float)(int32_t)reward + value) - prev_value;
+}
+
+// What one hit adds to acc for an error delta: clamped to +-2^20, in units of 2^-16, rounded to
+// nearest with ties to even (the default rounding mode), so |word| <= 2^36 and 2^26 hits of one
+// entry fit in acc. The value of llrintf(d * 65536), which is how HIP's llrintf is defined too.
+static constexpr float kNtDeltaClamp = 1048576.0f;   // 2^20
+static constexpr float kNtFixedOne = 65536.0f;       // acc counts delta in units of 2^-16
+
+R48_HD long long nt_fixed_delta(float delta)
+{
+    const float d = __builtin_fminf(__builtin_fmaxf(delta, -kNtDeltaClamp), kNtDeltaClamp);
+    return (long long)__builtin_rintf(d * kNtFixedOne);
+}
+
 // The mean of rate(e) over the board's 8m hits: fp32, summed from 0 in nt_value's order
 // p = 0 .. 8m - 1, one division by (float)(8m) at the end. The loads of one tuple's hits (8 of E,
 // 8 of A) are issued before their rates are formed.

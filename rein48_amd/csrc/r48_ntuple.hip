@@ -9,6 +9,8 @@
 //                    HBM on the way to the values.
 //   k_nt_accumulate  every hit (i, t, g) of a valid board: cnt[e] += 1, acc[e] += delta_i in
 //                    fixed point (2^-16) -- integer atomics, so the sums do not depend on order
+//   k_nt_td_act      k_nt_act on the env boards and, in the same launch, the trainer's TD error and
+//                    k_nt_accumulate for the previous step's afterstates: the fused training step
 //   k_nt_apply       every hit again: the one lane whose exchange takes the entry's count also
 //                    takes its sum and moves tables[e] by step * mean delta, once; both scratch
 //                    words are zero afterwards. No float atomics: bitwise reproducible.
@@ -38,8 +40,7 @@ void set_last_error(const std::string &msg);
 namespace {
 
 constexpr int kBlock = 256;
-constexpr float kDeltaClamp = 1048576.0f;   // 2^20
-constexpr float kFixedOne = 65536.0f;       // acc counts delta in units of 2^-16
+constexpr float kFixedOne = r48::kNtFixedOne;   // acc counts delta in units of 2^-16 (nt_fixed_delta)
 
 inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
@@ -120,6 +121,87 @@ __global__ __launch_bounds__(kBlock) void k_nt_act(const int8_t *__restrict__ bo
         legal[i] = (uint8_t)lg;
 }
 
+// One env step's act and the accumulate half of the TD update for the PREVIOUS afterstates, in one
+// launch (the trainer's fused step; apply and the env step follow as their own launches, apply
+// needs every sum finished). Lane i:
+//   - loads its env board, and issues the loads of its previous afterstate, value, done and valid
+//     flags right behind it: nothing needs them before the search is over, so they are in flight
+//     under it
+//   - runs k_nt_act's search, statement for statement (the same move_rows4, nt_value and
+//     first-maximiser rule: the same bits; written out again so that k_nt_act and its code
+//     objects stay what they are), and writes the chosen move's outputs; valid_out = the board
+//     had a move, i.e. this afterstate can be learned from at the next step
+//   - forms delta = nt_td_delta(...) from this step's reward and value, in registers
+//   - where prev_valid: walks the 8m hits of the previous afterstate with k_nt_accumulate's two
+//     integer atomics per hit
+// tables is only read: acc and cnt are the only words two lanes share, and integer sums do not
+// depend on their order, so the launch computes what act, the torch expression for delta and
+// accumulate compute one after another, bit for bit. after / value / valid_out must not be the
+// prev_ buffers (the entry point refuses it): apply reads the old ones after this kernel.
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_td_act(
+    const int8_t *__restrict__ boards, int64_t n, const r48::NtLayout lay, const float *__restrict__ tables,
+    const int8_t *__restrict__ prev_after, const float *__restrict__ prev_value, const uint8_t *__restrict__ prev_done,
+    const uint8_t *__restrict__ prev_valid, int8_t *__restrict__ actions, int8_t *__restrict__ after,
+    float *__restrict__ value, int32_t *__restrict__ reward, uint8_t *__restrict__ legal, uint8_t *__restrict__ valid_out,
+    float *__restrict__ delta_out, unsigned long long *__restrict__ acc, uint32_t *__restrict__ cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    const r48::Board b = r48::load_board(boards, i);
+    const r48::Board pb = r48::load_board(prev_after, i);
+    const float pv = prev_value[i];
+    const uint32_t pd = prev_done[i], pok = prev_valid[i];
+    const r48::Moves4 m = r48::move_rows4<true>(b);
+    const uint32_t lg = r48::nt_legal4(m, b);
+    // no legal move: action 0, the board itself, value 0, reward 0
+    r48::Board best_b = b;
+    float best_s = 0.0f, best_v = 0.0f;
+    uint32_t best_r = 0u, best_a = 0u;
+    bool have = false;
+#pragma unroll 1
+    for (uint32_t a = 0; a < 4u; a++) {
+        if (!((lg >> a) & 1u))
+            continue;
+        // a is uniform: scalar-conditioned selects, no indexed private array
+        const r48::Board c = a == 0u ? m.up : a == 1u ? m.down : a == 2u ? m.left : m.right;
+        const uint32_t r = a == 0u ? m.r_up : a == 1u ? m.r_down : a == 2u ? m.r_left : m.r_right;
+        const float v = r48::nt_value<L>(r48::nt_pack(c), lay, tables);
+        const float s = (float)(int32_t)r + v;
+        if (!have || s > best_s) {
+            have = true;
+            best_s = s;
+            best_v = v;
+            best_r = r;
+            best_a = a;
+            best_b = c;
+        }
+    }
+    actions[i] = (int8_t)best_a;
+    *reinterpret_cast<uint4 *>(after + 16 * i) = make_uint4(best_b.w0, best_b.w1, best_b.w2, best_b.w3);
+    value[i] = best_v;
+    if (reward)
+        reward[i] = (int32_t)best_r;
+    legal[i] = (uint8_t)lg;
+    valid_out[i] = lg != 0u ? 1 : 0;
+    const float delta = r48::nt_td_delta(pd, best_r, best_v, pv);
+    if (delta_out)
+        delta_out[i] = delta;
+    if (!pok)
+        return;
+    const r48::NtBoard p = r48::nt_pack(pb);
+    const unsigned long long q = (unsigned long long)r48::nt_fixed_delta(delta);   // two's complement: wraps as int64 adds
+    for (int t = 0; t < lay.m; t++) {
+#pragma unroll
+        for (int g = 0; g < r48::kNtSyms; g++) {
+            const uint32_t e = r48::nt_entry<L>(p, lay, r48::kNtSyms * t + g);
+            atomicAdd(&cnt[e], 1u);
+            atomicAdd(&acc[e], q);
+        }
+    }
+}
+
 template <int L>
 __global__ __launch_bounds__(kBlock) void k_nt_accumulate(const int8_t *__restrict__ boards, int64_t n,
                                                           const float *__restrict__ delta,
@@ -131,8 +213,7 @@ __global__ __launch_bounds__(kBlock) void k_nt_accumulate(const int8_t *__restri
     if (i >= n || (valid && !valid[i]))
         return;
     const r48::NtBoard b = r48::nt_pack(r48::load_board(boards, i));
-    const float d = fminf(fmaxf(delta[i], -kDeltaClamp), kDeltaClamp);
-    const unsigned long long q = (unsigned long long)llrintf(d * kFixedOne);   // two's complement: wraps as int64 adds
+    const unsigned long long q = (unsigned long long)r48::nt_fixed_delta(delta[i]);   // two's complement: wraps as int64 adds
     for (int t = 0; t < lay.m; t++) {
 #pragma unroll
         for (int g = 0; g < r48::kNtSyms; g++) {
@@ -496,6 +577,32 @@ int r48_ntuple_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_
         return R48_OK;
     R48_NT_DISPATCH(k_nt_act, boards, n, lay, tables, actions, after, value, reward, legal)
     return launched("k_nt_act");
+}
+
+int r48_ntuple_td_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                      const int8_t *prev_after, const float *prev_value, const uint8_t *prev_done,
+                      const uint8_t *prev_valid, int8_t *actions, int8_t *after, float *value, int32_t *reward,
+                      uint8_t *legal, uint8_t *valid_out, float *delta_out, int64_t *acc, uint32_t *cnt, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_common("r48_ntuple_td_act", boards, n, cells, m, L, lay))
+        return rc;
+    if (!tables || !prev_after || !prev_value || !prev_done || !prev_valid || !actions || !after || !value || !legal ||
+        !valid_out || !acc || !cnt)
+        return fail(R48_EINVAL, "r48_ntuple_td_act: tables, prev_after / prev_value / prev_done / prev_valid, actions, "
+                                "after, value, legal, valid_out, acc or cnt NULL (only reward and delta_out may be)");
+    if (!aligned(prev_after, 16) || !aligned(after, 16) || !aligned(acc, 8) || !aligned(tables, 4) ||
+        !aligned(prev_value, 4) || !aligned(value, 4) || !aligned(reward, 4) || !aligned(delta_out, 4) || !aligned(cnt, 4))
+        return fail(R48_EINVAL, "r48_ntuple_td_act: prev_after / after not 16-byte aligned, acc not 8-byte aligned, or "
+                                "tables / prev_value / value / reward / delta_out / cnt not 4-byte aligned");
+    if (after == prev_after || value == prev_value || valid_out == prev_valid)
+        return fail(R48_EINVAL, "r48_ntuple_td_act: after, value and valid_out must not be the prev_ buffers (apply "
+                                "reads the previous afterstates and flags after this call; swap the buffers then)");
+    if (n == 0)
+        return R48_OK;
+    R48_NT_DISPATCH(k_nt_td_act, boards, n, lay, tables, prev_after, prev_value, prev_done, prev_valid, actions, after,
+                    value, reward, legal, valid_out, delta_out, reinterpret_cast<unsigned long long *>(acc), cnt)
+    return launched("k_nt_td_act");
 }
 
 int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,

@@ -97,6 +97,34 @@ class NTupleNet:
                                        ptr(value), ptr(reward), ptr(legal), _stream(boards)))
         return actions, after, value, reward, legal
 
+    def td_act(self, boards, prev_after, prev_value, prev_done, prev_valid, actions=None, after=None, value=None,
+               reward=None, legal=None, valid=None, delta=None):
+        """act on `boards` and, in the same kernel, the accumulate half of the TD update for the
+        previous step's afterstates -> (actions, after, value, reward, legal) as act returns them,
+        valid uint8 [n] = legal != 0, and delta float32 [n] = (0 where prev_done else reward +
+        value) - prev_value for every board. Boards with prev_valid != 0 add delta over the hits of
+        prev_after into the net's scratch; apply(prev_after, step, prev_valid) finishes the update.
+        after / value / valid must not be the prev_ tensors: apply still reads those."""
+        n = _boards(boards)
+        if _boards(prev_after) != n:
+            raise ValueError("prev_after must hold one afterstate per board (%d)" % n)
+        for t, name, dtype in ((prev_value, "prev_value", torch.float32), (prev_done, "prev_done", torch.uint8),
+                               (prev_valid, "prev_valid", torch.uint8)):
+            if _dev(t, name, dtype).numel() != n:
+                raise ValueError("%s must have one element per board (%d)" % (name, n))
+        actions = _out(actions, "actions", torch.int8, (n,), boards)
+        after = _out(after, "after", torch.int8, (n, 16), boards)
+        value = _out(value, "value", torch.float32, (n,), boards)
+        reward = _out(reward, "reward", torch.int32, (n,), boards)
+        legal = _out(legal, "legal", torch.uint8, (n,), boards)
+        valid = _out(valid, "valid", torch.uint8, (n,), boards)
+        delta = _out(delta, "delta", torch.float32, (n,), boards)
+        check(self._lib.r48_ntuple_td_act(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(prev_after),
+                                          ptr(prev_value), ptr(prev_done), ptr(prev_valid), ptr(actions), ptr(after),
+                                          ptr(value), ptr(reward), ptr(legal), ptr(valid), ptr(delta), ptr(self.acc),
+                                          ptr(self.cnt), _stream(boards)))
+        return actions, after, value, reward, legal, valid, delta
+
     def accumulate(self, boards, delta, valid=None):
         """First half of td_update: per-entry hit counts and fixed-point delta sums into the scratch."""
         n = _boards(boards)
@@ -215,6 +243,7 @@ class NTupleConfig:
     alpha: float = 0.25
     seed: int = 0
     tc: bool = False                 # temporal-coherence learning rates; alpha = 1.0 is recommended with it
+    fused: bool = False              # train_step in three launches (td_act, apply, env.step): the same bits
 
 
 class NTupleTrainer:
@@ -225,6 +254,10 @@ class NTupleTrainer:
          (one batch update old); td_update(s'_{t-1}, delta, alpha, valid)
       3. env.step(a_t, auto_reset=True); s'_t, v_t, done become the "previous"
     cfg.tc: the update scales every entry's step by its temporal-coherence rate (NTupleNet).
+    cfg.fused: steps 1 and 2 up to the sums run in one kernel (NTupleNet.td_act), apply and the env
+    step follow, and the "previous" buffers are swapped by reference: three launches and no torch
+    kernel instead of about fourteen, the same bits in every tensor, so a checkpoint moves freely
+    between the two paths.
     No exploration: the spawns randomise. Single GPU (an all-reduce of the table updates is not
     built)."""
 
@@ -245,13 +278,24 @@ class NTupleTrainer:
         self.after, self.prev_after = (torch.zeros((n, 16), dtype=torch.int8, device=d) for _ in range(2))
         self.value, self.prev_value = (torch.zeros(n, dtype=torch.float32, device=d) for _ in range(2))
         self.prev_done = torch.zeros(n, dtype=torch.uint8, device=d)
-        self.prev_valid = torch.zeros(n, dtype=torch.uint8, device=d)   # the first step has no previous afterstate
+        # 0/1; the first step has no previous afterstate. `valid` is the fused step's output, swapped with it
+        self.valid, self.prev_valid = (torch.zeros(n, dtype=torch.uint8, device=d) for _ in range(2))
         self.delta = torch.zeros(n, dtype=torch.float32, device=d)
         self.updates = 0
 
     @torch.no_grad()
     def train_step(self):
         net, env = self.net, self.env
+        if self.cfg.fused:
+            net.td_act(env.boards, self.prev_after, self.prev_value, self.prev_done, self.prev_valid, self.actions,
+                       self.after, self.value, self.reward, self.legal, self.valid, self.delta)
+            net.apply(self.prev_after, self.cfg.alpha / (8.0 * net.m), self.prev_valid)
+            env.step(self.actions, auto_reset=True, done_out=self.prev_done)
+            self.after, self.prev_after = self.prev_after, self.after
+            self.value, self.prev_value = self.prev_value, self.value
+            self.valid, self.prev_valid = self.prev_valid, self.valid
+            self.updates += 1
+            return
         net.act(env.boards, self.actions, self.after, self.value, self.reward, self.legal)
         target = torch.where(self.prev_done != 0, torch.zeros_like(self.value), self.reward.float() + self.value)
         torch.sub(target, self.prev_value, out=self.delta)
@@ -262,6 +306,11 @@ class NTupleTrainer:
         self.prev_done.copy_(done)
         self.prev_valid.copy_(self.legal != 0)   # an afterstate exists where a move did
         self.updates += 1
+
+    def train_steps(self, k):
+        """k train_step()s in one Python call."""
+        for _ in range(int(k)):
+            self.train_step()
 
     def policy(self, depth=1):
         return self.net.policy(depth)

@@ -4,6 +4,7 @@
     python tools/exp_ntuple.py --search [--out DIR] [--sizes 4096,65536] [--scores] [--long]
     python tools/exp_ntuple.py --tc [--out DIR] [--sizes 65536,1048576] [--scores]
     python tools/exp_ntuple.py --search3 [--out DIR] [--sizes 256,4096,16384] [--scores] [--episodes N] [--ab-lib SO]
+    python tools/exp_ntuple.py --fused [--out DIR] [--sizes 1024,4096,65536,1048576] [--scores] [--episodes N]
 
 For both named layouts and each board count: device-event times (5 warm-up calls, median of 7
 windows of 20 calls) of value, act, accumulate and apply with their table loads or atomics per
@@ -45,6 +46,16 @@ trainer against a TC one -- once with alpha 0 for both (frozen zero tables: the 
 games, so each pair of windows sees the same boards) and once with the recipes' alphas. With --scores: TD(0) alpha 0.25 against TC alpha 1.0 at depth 1 and 2 for
 lines-squares and 4x6 at 1,024 x 2,000 steps and 4x6 at 4,096 x 10,000, 4,096 episodes, eval seed
 13, and the 1,024 x 1,000 lines-squares recipe of the learning test. Writes exp_ntuple_tc.json.
+
+--fused: the fused training step (NTupleConfig.fused: td_act, apply, env.step) against the unfused
+one of the same build. For both layouts, each board count (default 1,024, 4,096, 2^16 and 2^20) and
+TD (alpha 0.25) and TC (alpha 1.0): a fused and an unfused trainer from the same seed -- they are
+bit-identical, which is checked at the end, so each pair of windows sees the same boards -- stepped
+in alternated windows on the host clock (20 warm-up steps each, median of 7 windows of 20 steps and
+a synchronise), with the windows' min-max spread next to the difference. Then device-event times of
+td_act against act + accumulate, act and accumulate on the same inputs. With --scores: the 4x6 TC
+recipe (4,096 boards, alpha 1.0, seed 0) for 10,000 unfused steps, the fused steps that fit in the
+same wall time, and the depth-1 score of each (--episodes, eval seed 13). Writes exp_ntuple_fused.json.
 """
 import argparse
 import json
@@ -492,6 +503,188 @@ def main_search3(args):
             save()
 
 
+def alternated_host_ms(fns, warmup=20, windows=7, calls=20):
+    """alternated_ms on the host clock: every window is `calls` calls and a synchronise, as a
+    training loop pays for them -- ({name: the windows' times in order}, {name: the median time
+    until the last call returned, before the synchronise: what the host spends enqueueing}) in ms
+    per call."""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    out, enq = {k: [] for k in fns}, {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                fn()
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            out[k].append((time.perf_counter() - t0) / calls * 1e3)
+            enq[k].append((t1 - t0) / calls * 1e3)
+    return out, {k: statistics.median(v) for k, v in enq.items()}
+
+
+def fused_windows(w):
+    """The comparison of one set of alternated windows {"unfused": [...], "fused": [...]}: medians,
+    the larger of the two min-max spreads next to the median saving (the spread holds whatever
+    changes from window to window, the games' progress included: all boards start from reset
+    together), and the differences within the pairs of windows, which saw the same boards."""
+    u, f = w["unfused"], w["fused"]
+    mu, mf = statistics.median(u), statistics.median(f)
+    spread = max(max(u) - min(u), max(f) - min(f))
+    pairs = [a - b for a, b in zip(u, f)]
+    return {"unfused": {"ms": mu, "ms_min": min(u), "ms_max": max(u), "windows_ms": u},
+            "fused": {"ms": mf, "ms_min": min(f), "ms_max": max(f), "windows_ms": f},
+            "unfused_over_fused": mu / mf, "saved_ms": mu - mf, "largest_min_max_spread_ms": spread,
+            "saving_exceeds_spread": mu - mf > spread, "not_slower_by_more_than_spread": mf - mu <= spread,
+            "paired_saving_ms": {"median": statistics.median(pairs), "min": min(pairs), "max": max(pairs)},
+            "fused_faster_in_pairs": sum(p > 0 for p in pairs), "pairs": len(pairs)}
+
+
+def fused_train_step(layout, n, tc):
+    """A fused and an unfused trainer from the same seed with the recipe's alpha: bit-identical, so
+    both see the same boards at the same step of every pair of windows."""
+    alpha = 1.0 if tc else 0.25
+    trs = {k: NTupleTrainer(NTupleConfig(n_boards=n, layout=layout, alpha=alpha, seed=3, tc=tc, fused=k == "fused"), device=DEV)
+           for k in ("unfused", "fused")}
+    w, enq = alternated_host_ms({k: tr.train_step for k, tr in trs.items()})
+    res = {"layout": layout, "boards": n, "tc": tc, "alpha": alpha}
+    res.update(fused_windows(w))
+    res.update(env_steps_per_s_unfused=n / (res["unfused"]["ms"] * 1e-3), env_steps_per_s_fused=n / (res["fused"]["ms"] * 1e-3),
+               host_enqueue_ms_unfused=enq["unfused"], host_enqueue_ms_fused=enq["fused"])
+    if n <= 4096:                                            # ten times longer windows, next to the prescribed ones
+        res["windows_of_200_steps"] = fused_windows(alternated_host_ms({k: tr.train_step for k, tr in trs.items()}, warmup=0,
+                                                                       calls=200)[0])
+    u, f = trs["unfused"], trs["fused"]
+    res["steps_each"] = u.updates
+    res["bit_identical_at_the_end"] = bool(
+        u.updates == f.updates and torch.equal(u.env.boards, f.env.boards)
+        and torch.equal(u.net.tables.view(torch.int32), f.net.tables.view(torch.int32))
+        and torch.equal(u.prev_value.view(torch.int32), f.prev_value.view(torch.int32)))
+    del trs, u, f
+    torch.cuda.empty_cache()
+    return res
+
+
+def fused_kernels(layout, n):
+    """Device-event times of td_act against act and accumulate on the same inputs: boards of running
+    games, their previous step's afterstates and values, every row valid. The sums in the scratch
+    grow over the timed calls; the integer adds cost the same."""
+    net = NTupleNet(layout, device=DEV)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    net.tables.copy_(torch.randn(net.tables.shape, generator=g, device=DEV) * 30.0)
+    env = VecGame(n, device=DEV, seed=7)
+    env.reset()
+    greedy = afterstate_policy(None)
+    for t in range(150):
+        env.step(greedy(env.boards, t), auto_reset=True)
+    a, prev_after, prev_value, r, legal = net.act(env.boards)
+    prev_done = env.step(a, auto_reset=True)[2].clone()
+    boards = env.boards.clone()
+    prev_valid = torch.ones(n, dtype=torch.uint8, device=DEV)
+    after, value = torch.empty_like(prev_after), torch.empty_like(prev_value)
+    valid, delta = torch.empty_like(prev_valid), torch.empty_like(prev_value)
+    net.act(boards, a, after, value, r, legal)
+    delta.copy_(torch.where(prev_done != 0, torch.zeros_like(value), r.float() + value) - prev_value)
+
+    def pair():
+        net.act(boards, a, after, value, r, legal)
+        net.accumulate(prev_after, delta, prev_valid)
+    def td_act():
+        net.td_act(boards, prev_after, prev_value, prev_done, prev_valid, a, after, value, r, legal, valid, delta)
+
+    def glue():                                              # the unfused step's torch kernels between act and accumulate
+        target = torch.where(prev_done != 0, torch.zeros_like(value), r.float() + value)
+        torch.sub(target, prev_value, out=delta)
+
+    def update():                                            # the fused step's first two launches: the scratch is zero again
+        td_act()
+        net.apply(prev_after, 0.25 / (8.0 * net.m), prev_valid)
+    t = alternated_ms({"td_act": td_act, "act_accumulate": pair, "act": lambda: net.act(boards, a, after, value, r, legal),
+                       "accumulate": lambda: net.accumulate(prev_after, delta, prev_valid), "torch_glue": glue})
+    net.acc.zero_()
+    net.cnt.zero_()
+    acts = a.clone()                                         # the moves of the boards the env holds now
+    t.update(alternated_ms({"td_act_apply": update, "env_step": lambda: env.step(acts, auto_reset=True)}))
+    res = {"layout": layout, "boards": n, "tuples": net.m, "length": net.L, "hits": 8 * net.m * n}
+    res.update({k: _ms(v) for k, v in t.items()})
+    res["act_accumulate_over_td_act"] = t["act_accumulate"][0] / t["td_act"][0]
+    res["td_act_minus_accumulate_ms"] = t["td_act"][0] - t["accumulate"][0]
+    res["apply"] = {"ms": max(t["td_act_apply"][0] - t["td_act"][0], 1e-6), "derived": "td_act_apply - td_act"}
+    res["three_kernels_ms"] = t["td_act_apply"][0] + t["env_step"][0]
+    del net
+    torch.cuda.empty_cache()
+    return res
+
+
+def fused_budget(layout="4x6", n_boards=4096, steps=10000, eval_seed=13, episodes=4096):
+    """What the saved time buys: the unfused TC recipe's wall time for `steps` steps, the number of
+    fused steps that fit in the same time, and the depth-1 score each reaches."""
+    def evaluate(tr, row):
+        ev = play_episodes(tr.policy(depth=1), episodes, device=DEV, seed=eval_seed, return_scores=True)
+        sc = ev.pop("scores").numpy()
+        ev["score_std"] = float(sc.std(ddof=1))
+        ev["standard_error"] = ev["score_std"] / episodes ** 0.5
+        row["depth1"] = ev
+        return row
+    out = {"layout": layout, "train_boards": n_boards, "alpha": 1.0, "tc": True, "eval_seed": eval_seed, "episodes": episodes}
+    tr = NTupleTrainer(NTupleConfig(n_boards=n_boards, layout=layout, alpha=1.0, seed=0, tc=True), device=DEV)
+    tr.train_steps(200)                                      # code objects loaded, clocks up; part of the budget's steps
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tr.train_steps(steps - 200)
+    torch.cuda.synchronize()
+    budget = time.perf_counter() - t0
+    out["unfused"] = evaluate(tr, {"train_steps": tr.updates, "timed_steps": steps - 200, "timed_seconds": budget})
+    del tr
+    torch.cuda.empty_cache()
+    tr = NTupleTrainer(NTupleConfig(n_boards=n_boards, layout=layout, alpha=1.0, seed=0, tc=True, fused=True), device=DEV)
+    tr.train_steps(200)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    while True:                                              # 100 steps and a synchronise at a time, until the budget is spent
+        tr.train_steps(100)
+        torch.cuda.synchronize()
+        spent = time.perf_counter() - t0
+        if spent >= budget:
+            break
+    out["fused"] = evaluate(tr, {"train_steps": tr.updates, "timed_steps": tr.updates - 200, "timed_seconds": spent})
+    out["fused_steps_over_unfused_steps"] = out["fused"]["timed_steps"] / out["unfused"]["timed_steps"]
+    a, b = out["fused"]["depth1"], out["unfused"]["depth1"]
+    se = (a["standard_error"] ** 2 + b["standard_error"] ** 2) ** 0.5
+    out["fused_minus_unfused_in_standard_errors"] = (a["mean_score"] - b["mean_score"]) / se
+    del tr
+    torch.cuda.empty_cache()
+    return out
+
+
+def main_fused(args):
+    out = {"device": torch.cuda.get_device_name(0), "train_step": [], "kernels": [], "budget": []}
+
+    def save():
+        if args.out:
+            os.makedirs(args.out, exist_ok=True)
+            with open(os.path.join(args.out, "exp_ntuple_fused.json"), "w") as f:
+                json.dump(out, f, indent=1)
+    sizes = [int(s) for s in (args.sizes or "1024,4096,65536,1048576").split(",")]
+    for layout in ("lines-squares", "4x6"):
+        for n in sizes:
+            for tc in (False, True):
+                r = fused_train_step(layout, n, tc)
+                out["train_step"].append(r)
+                print(json.dumps(r), flush=True)
+            r = fused_kernels(layout, n)
+            out["kernels"].append(r)
+            print(json.dumps(r), flush=True)
+            save()
+    if args.scores:
+        r = fused_budget(episodes=args.episodes)
+        out["budget"].append(r)
+        print(json.dumps(r), flush=True)
+        save()
+
+
 def main_search(args):
     out = {"device": torch.cuda.get_device_name(0), "kernels": [], "scores": []}
     for layout in ("lines-squares", "4x6"):
@@ -520,11 +713,14 @@ def main():
     ap.add_argument("--long", action="store_true")
     ap.add_argument("--tc", action="store_true")
     ap.add_argument("--search3", action="store_true")
+    ap.add_argument("--fused", action="store_true")
     ap.add_argument("--episodes", type=int, default=4096)
     ap.add_argument("--ab-lib", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("exp_ntuple.py needs a GPU")
+    if args.fused:
+        return main_fused(args)
     if args.search3:
         return main_search3(args)
     if args.search:
