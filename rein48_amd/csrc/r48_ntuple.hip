@@ -1,32 +1,28 @@
 // r48_ntuple.hip -- the n-tuple network (r48_ntuple.h) behind include/rein48.h: value, the fused
-// one-ply afterstate search, and the two halves of the per-entry-mean TD update. Stateless like
-// r48_moves.hip: plain device pointers plus the layout's cells on the host.
+// one-ply afterstate search, the expectimax searches and the per-entry-mean TD update. Stateless
+// like r48_moves.hip: plain device pointers plus the layout's cells on the host.
 //
-//   k_nt_value       board -> V(board): 8m table gathers, fp32 sum in the header's fixed order
-//   k_nt_act         board -> the four moves in registers (move_rows4), V of the legal ones only,
-//                    argmax of reward + V with ties to the lowest code; writes the chosen move's
-//                    afterstate / V / reward and the legal set. No afterstate plane goes through
-//                    HBM on the way to the values.
-//   k_nt_accumulate  every hit (i, t, g) of a valid board: cnt[e] += 1, acc[e] += delta_i in
-//                    fixed point (2^-16) -- integer atomics, so the sums do not depend on order
-//   k_nt_td_act      k_nt_act on the env boards and, in the same launch, the trainer's TD error and
-//                    k_nt_accumulate for the previous step's afterstates: the fused training step
-//   k_nt_apply       every hit again: the one lane whose exchange takes the entry's count also
-//                    takes its sum and moves tables[e] by step * mean delta, once; both scratch
-//                    words are zero afterwards. No float atomics: bitwise reproducible.
-//   k_nt_apply_tc    apply with temporal-coherence learning rates: the owner lane also owns the
-//                    entry's error sums E[e], A[e] and scales its step by |E| / A
-//   k_nt_tc_rate     board -> the mean learning rate |E| / A over its 8m hits (read-only)
-//   k_nt_search      board -> the four action values Q and their first argmax at depth 1 (act's
-//                    scores) or depth 2 (expectimax over the tile spawn); one board per WAVE
-//   k_nt_search3     the same three plies deep: one board per WORKGROUP, whose waves search the
-//                    board's children with depth 2's wave-level routine
-// Otherwise one board per lane, one 16-byte board load; templated on the tuple length L so the cell loops
-// unroll; the expanded layout travels by value in the kernel arguments (wave-uniform).
+// Every body is stated once, as a __forceinline__ device routine, and the kernels are those
+// routines behind a board load and their stores:
+//   nt_act_board     the one-ply search of a board in one lane   k_nt_act, k_nt_td_act
+//   nt_add_hits      cnt[e] += 1, acc[e] += delta over 8m hits   k_nt_accumulate, k_nt_td_act
+//   nt_owned_hits    the exchange walk that finds an entry's     k_nt_apply (plain mean step),
+//                    one owner lane                              k_nt_apply_tc (TC rule)
+//   nt_wave_q2       the depth-2 search of a board by a wave     k_nt_search<L, 2>, k_nt_search3
+//   nt_row_q,        how a search ends: butterfly, Q, the four   nt_wave_q2, k_nt_search,
+//   nt_write_search  rows' scores, argmax, the writes            k_nt_search3
+// and r48_ntuple.h's nt_value (k_nt_value and everything above) and nt_tc_rate_mean (k_nt_tc_rate).
+// k_nt_td_act is act, the trainer's TD error and accumulate for the previous step's afterstates in
+// one launch: the fused training step. k_nt_search runs one board per WAVE, k_nt_search3 one per
+// WORKGROUP; every other kernel one board per lane with one 16-byte board load. All are templated
+// on the tuple length L so the cell loops unroll; the expanded layout travels by value in the
+// kernel arguments (wave-uniform).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
 #include <string>
+#include <type_traits>
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
@@ -40,7 +36,6 @@ void set_last_error(const std::string &msg);
 namespace {
 
 constexpr int kBlock = 256;
-constexpr float kFixedOne = r48::kNtFixedOne;   // acc counts delta in units of 2^-16 (nt_fixed_delta)
 
 inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
@@ -73,21 +68,22 @@ __global__ __launch_bounds__(kBlock) void k_nt_value(const int8_t *__restrict__ 
     value[i] = r48::nt_value<L>(r48::nt_pack(r48::load_board(boards, i)), lay, tables);
 }
 
+// the move the one-ply search chooses
+struct NtMove {
+    r48::Board after;
+    float value;
+    uint32_t reward, action, legal;
+};
+
+// The one-ply search of one board in one lane: the four moves in registers (move_rows4), V of the
+// legal ones only, the first maximiser of reward + V. No legal move: action 0, the board itself,
+// value 0, reward 0.
 template <int L>
-__global__ __launch_bounds__(kBlock) void k_nt_act(const int8_t *__restrict__ boards, int64_t n,
-                                                   const r48::NtLayout lay, const float *__restrict__ tables,
-                                                   int8_t *__restrict__ actions, int8_t *__restrict__ after,
-                                                   float *__restrict__ value, int32_t *__restrict__ reward,
-                                                   uint8_t *__restrict__ legal)
+__device__ __forceinline__ NtMove nt_act_board(const r48::Board &b, const r48::NtLayout &lay,
+                                               const float *__restrict__ tables)
 {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n)
-        return;
-    const r48::Board b = r48::load_board(boards, i);
     const r48::Moves4 m = r48::move_rows4<true>(b);
-    const uint32_t lg = (r48::differs(m.up, b) ? 1u : 0u) | (r48::differs(m.down, b) ? 2u : 0u) |
-                        (r48::differs(m.left, b) ? 4u : 0u) | (r48::differs(m.right, b) ? 8u : 0u);
-    // no legal move: action 0, the board itself, value 0, reward 0
+    const uint32_t lg = r48::nt_legal4(m, b);
     r48::Board best_b = b;
     float best_s = 0.0f, best_v = 0.0f;
     uint32_t best_r = 0u, best_a = 0u;
@@ -110,15 +106,46 @@ __global__ __launch_bounds__(kBlock) void k_nt_act(const int8_t *__restrict__ bo
             best_b = c;
         }
     }
-    actions[i] = (int8_t)best_a;
+    return NtMove{best_b, best_v, best_r, best_a, lg};
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_act(const int8_t *__restrict__ boards, int64_t n,
+                                                   const r48::NtLayout lay, const float *__restrict__ tables,
+                                                   int8_t *__restrict__ actions, int8_t *__restrict__ after,
+                                                   float *__restrict__ value, int32_t *__restrict__ reward,
+                                                   uint8_t *__restrict__ legal)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    const NtMove mv = nt_act_board<L>(r48::load_board(boards, i), lay, tables);
+    actions[i] = (int8_t)mv.action;
     if (after)
-        *reinterpret_cast<uint4 *>(after + 16 * i) = make_uint4(best_b.w0, best_b.w1, best_b.w2, best_b.w3);
+        *reinterpret_cast<uint4 *>(after + 16 * i) = make_uint4(mv.after.w0, mv.after.w1, mv.after.w2, mv.after.w3);
     if (value)
-        value[i] = best_v;
+        value[i] = mv.value;
     if (reward)
-        reward[i] = (int32_t)best_r;
+        reward[i] = (int32_t)mv.reward;
     if (legal)
-        legal[i] = (uint8_t)lg;
+        legal[i] = (uint8_t)mv.legal;
+}
+
+// The accumulate half of the update for one board: every hit (t, g) adds 1 to cnt[e] and delta in
+// fixed point to acc[e]. Integer atomics, so the sums do not depend on the order of the lanes.
+template <int L>
+__device__ __forceinline__ void nt_add_hits(const r48::NtBoard &b, const r48::NtLayout &lay, float delta,
+                                            unsigned long long *__restrict__ acc, uint32_t *__restrict__ cnt)
+{
+    const unsigned long long q = (unsigned long long)r48::nt_fixed_delta(delta);   // two's complement: wraps as int64 adds
+    for (int t = 0; t < lay.m; t++) {
+#pragma unroll
+        for (int g = 0; g < r48::kNtSyms; g++) {
+            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g);
+            atomicAdd(&cnt[e], 1u);
+            atomicAdd(&acc[e], q);
+        }
+    }
 }
 
 // One env step's act and the accumulate half of the TD update for the PREVIOUS afterstates, in one
@@ -127,13 +154,10 @@ __global__ __launch_bounds__(kBlock) void k_nt_act(const int8_t *__restrict__ bo
 //   - loads its env board, and issues the loads of its previous afterstate, value, done and valid
 //     flags right behind it: nothing needs them before the search is over, so they are in flight
 //     under it
-//   - runs k_nt_act's search, statement for statement (the same move_rows4, nt_value and
-//     first-maximiser rule: the same bits; written out again so that k_nt_act and its code
-//     objects stay what they are), and writes the chosen move's outputs; valid_out = the board
+//   - runs act's search (nt_act_board) and writes the chosen move's outputs; valid_out = the board
 //     had a move, i.e. this afterstate can be learned from at the next step
 //   - forms delta = nt_td_delta(...) from this step's reward and value, in registers
-//   - where prev_valid: walks the 8m hits of the previous afterstate with k_nt_accumulate's two
-//     integer atomics per hit
+//   - where prev_valid: accumulate's walk (nt_add_hits) over the previous afterstate
 // tables is only read: acc and cnt are the only words two lanes share, and integer sums do not
 // depend on their order, so the launch computes what act, the torch expression for delta and
 // accumulate compute one after another, bit for bit. after / value / valid_out must not be the
@@ -153,53 +177,19 @@ __global__ __launch_bounds__(kBlock) void k_nt_td_act(
     const r48::Board pb = r48::load_board(prev_after, i);
     const float pv = prev_value[i];
     const uint32_t pd = prev_done[i], pok = prev_valid[i];
-    const r48::Moves4 m = r48::move_rows4<true>(b);
-    const uint32_t lg = r48::nt_legal4(m, b);
-    // no legal move: action 0, the board itself, value 0, reward 0
-    r48::Board best_b = b;
-    float best_s = 0.0f, best_v = 0.0f;
-    uint32_t best_r = 0u, best_a = 0u;
-    bool have = false;
-#pragma unroll 1
-    for (uint32_t a = 0; a < 4u; a++) {
-        if (!((lg >> a) & 1u))
-            continue;
-        // a is uniform: scalar-conditioned selects, no indexed private array
-        const r48::Board c = a == 0u ? m.up : a == 1u ? m.down : a == 2u ? m.left : m.right;
-        const uint32_t r = a == 0u ? m.r_up : a == 1u ? m.r_down : a == 2u ? m.r_left : m.r_right;
-        const float v = r48::nt_value<L>(r48::nt_pack(c), lay, tables);
-        const float s = (float)(int32_t)r + v;
-        if (!have || s > best_s) {
-            have = true;
-            best_s = s;
-            best_v = v;
-            best_r = r;
-            best_a = a;
-            best_b = c;
-        }
-    }
-    actions[i] = (int8_t)best_a;
-    *reinterpret_cast<uint4 *>(after + 16 * i) = make_uint4(best_b.w0, best_b.w1, best_b.w2, best_b.w3);
-    value[i] = best_v;
+    const NtMove mv = nt_act_board<L>(b, lay, tables);
+    actions[i] = (int8_t)mv.action;
+    *reinterpret_cast<uint4 *>(after + 16 * i) = make_uint4(mv.after.w0, mv.after.w1, mv.after.w2, mv.after.w3);
+    value[i] = mv.value;
     if (reward)
-        reward[i] = (int32_t)best_r;
-    legal[i] = (uint8_t)lg;
-    valid_out[i] = lg != 0u ? 1 : 0;
-    const float delta = r48::nt_td_delta(pd, best_r, best_v, pv);
+        reward[i] = (int32_t)mv.reward;
+    legal[i] = (uint8_t)mv.legal;
+    valid_out[i] = mv.legal != 0u ? 1 : 0;
+    const float delta = r48::nt_td_delta(pd, mv.reward, mv.value, pv);
     if (delta_out)
         delta_out[i] = delta;
-    if (!pok)
-        return;
-    const r48::NtBoard p = r48::nt_pack(pb);
-    const unsigned long long q = (unsigned long long)r48::nt_fixed_delta(delta);   // two's complement: wraps as int64 adds
-    for (int t = 0; t < lay.m; t++) {
-#pragma unroll
-        for (int g = 0; g < r48::kNtSyms; g++) {
-            const uint32_t e = r48::nt_entry<L>(p, lay, r48::kNtSyms * t + g);
-            atomicAdd(&cnt[e], 1u);
-            atomicAdd(&acc[e], q);
-        }
-    }
+    if (pok)
+        nt_add_hits<L>(r48::nt_pack(pb), lay, delta, acc, cnt);
 }
 
 template <int L>
@@ -212,18 +202,34 @@ __global__ __launch_bounds__(kBlock) void k_nt_accumulate(const int8_t *__restri
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n || (valid && !valid[i]))
         return;
-    const r48::NtBoard b = r48::nt_pack(r48::load_board(boards, i));
-    const unsigned long long q = (unsigned long long)r48::nt_fixed_delta(delta[i]);   // two's complement: wraps as int64 adds
+    nt_add_hits<L>(r48::nt_pack(r48::load_board(boards, i)), lay, delta[i], acc, cnt);
+}
+
+// The apply half: every hit again. The one lane of the launch whose exchange takes an entry's
+// count owns the entry: update(e, count) runs once per entry hit, in that lane, and takes the
+// entry's sum with nt_take_sum. Both scratch words are zero afterwards.
+template <int L, class Update>
+__device__ __forceinline__ void nt_owned_hits(const r48::NtBoard &b, const r48::NtLayout &lay,
+                                              uint32_t *__restrict__ cnt, Update update)
+{
     for (int t = 0; t < lay.m; t++) {
 #pragma unroll
         for (int g = 0; g < r48::kNtSyms; g++) {
             const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g);
-            atomicAdd(&cnt[e], 1u);
-            atomicAdd(&acc[e], q);
+            const uint32_t c = atomicExch(&cnt[e], 0u);
+            if (c != 0u)
+                update(e, c);
         }
     }
 }
 
+__device__ __forceinline__ long long nt_take_sum(unsigned long long *__restrict__ acc, uint32_t e)
+{
+    return (long long)atomicExch(&acc[e], 0ull);
+}
+
+// The owner moves tables[e] by step * the mean delta of the entry's hits, once. No float atomics:
+// bitwise reproducible.
 template <int L>
 __global__ __launch_bounds__(kBlock) void k_nt_apply(const int8_t *__restrict__ boards, int64_t n,
                                                      const uint8_t *__restrict__ valid, const r48::NtLayout lay,
@@ -233,26 +239,15 @@ __global__ __launch_bounds__(kBlock) void k_nt_apply(const int8_t *__restrict__ 
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n || (valid && !valid[i]))
         return;
-    const r48::NtBoard b = r48::nt_pack(r48::load_board(boards, i));
-    for (int t = 0; t < lay.m; t++) {
-#pragma unroll
-        for (int g = 0; g < r48::kNtSyms; g++) {
-            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g);
-            const uint32_t c = atomicExch(&cnt[e], 0u);
-            if (c != 0u) {
-                // the only lane of this launch that sees a count for e: it owns tables[e]
-                const long long a = (long long)atomicExch(&acc[e], 0ull);
-                tables[e] += step * (((float)a * (1.0f / kFixedOne)) / (float)c);
-            }
-        }
-    }
+    nt_owned_hits<L>(r48::nt_pack(r48::load_board(boards, i)), lay, cnt,
+                     [&](uint32_t e, uint32_t c) { tables[e] += step * r48::nt_mean(nt_take_sum(acc, e), c); });
 }
 
-// apply with temporal-coherence learning rates (r48_ntuple.h): the lane that takes an entry's
-// count owns tables[e], E[e] and A[e] for this launch. Its three loads are issued together, the
-// rule runs in registers, three plain stores follow. The sums are order-free integers and the
-// owner's arithmetic does not depend on which lane it is, so all three tables are bitwise
-// reproducible and independent of the boards' order in the batch.
+// apply with temporal-coherence learning rates (r48_ntuple.h): the owner of an entry also owns
+// E[e] and A[e] for this launch. Its three loads are issued together, the rule runs in registers,
+// three plain stores follow. The sums are order-free integers and the owner's arithmetic does not
+// depend on which lane it is, so all three tables are bitwise reproducible and independent of the
+// boards' order in the batch.
 template <int L>
 __global__ __launch_bounds__(kBlock) void k_nt_apply_tc(const int8_t *__restrict__ boards, int64_t n,
                                                         const uint8_t *__restrict__ valid, const r48::NtLayout lay,
@@ -264,22 +259,13 @@ __global__ __launch_bounds__(kBlock) void k_nt_apply_tc(const int8_t *__restrict
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n || (valid && !valid[i]))
         return;
-    const r48::NtBoard b = r48::nt_pack(r48::load_board(boards, i));
-    for (int t = 0; t < lay.m; t++) {
-#pragma unroll
-        for (int g = 0; g < r48::kNtSyms; g++) {
-            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g);
-            const uint32_t c = atomicExch(&cnt[e], 0u);
-            if (c != 0u) {
-                float w = tables[e], se = tc_e[e], sa = tc_a[e];
-                const long long a = (long long)atomicExch(&acc[e], 0ull);
-                r48::nt_tc_update(w, se, sa, r48::nt_mean(a, c), step);
-                tables[e] = w;
-                tc_e[e] = se;
-                tc_a[e] = sa;
-            }
-        }
-    }
+    nt_owned_hits<L>(r48::nt_pack(r48::load_board(boards, i)), lay, cnt, [&](uint32_t e, uint32_t c) {
+        float w = tables[e], se = tc_e[e], sa = tc_a[e];
+        r48::nt_tc_update(w, se, sa, r48::nt_mean(nt_take_sum(acc, e), c), step);
+        tables[e] = w;
+        tc_e[e] = se;
+        tc_a[e] = sa;
+    });
 }
 
 // How settled the network is on a set of boards: the mean learning rate over each board's hits.
@@ -312,7 +298,34 @@ __global__ __launch_bounds__(kBlock) void k_nt_tc_rate(const int8_t *__restrict_
 // read from lanes 0, 16, 32, 48; those lanes write q, lane 0 the action and the legal set.
 constexpr int kSearchBoards = kBlock / 64;   // boards (waves) per workgroup
 
-// The depth-2 search of a board that every lane of the wave holds (the comment above): the
+// How a search at depth 2 or 3 ends in lane 16 a + c: S_a by the xor butterfly over the row's
+// cell terms x, then the header's Q(a); -inf where move a is illegal.
+__device__ __forceinline__ float nt_row_q(float x, bool ok, uint32_t reward, const r48::Board &afterstate)
+{
+    x += __shfl_xor(x, 1);
+    x += __shfl_xor(x, 2);
+    x += __shfl_xor(x, 4);
+    x += __shfl_xor(x, 8);
+    return ok ? r48::nt_q2(reward, x, r48::blanks(afterstate).n) : -__builtin_inff();
+}
+
+// What every search writes for board i from the rows' scores qa: the first lane of each row its
+// q, lane 0 the first maximiser and the legal set.
+__device__ __forceinline__ void nt_write_search(float qa, uint32_t lane, uint32_t lg, int64_t i,
+                                                int8_t *__restrict__ actions, float *__restrict__ q,
+                                                uint8_t *__restrict__ legal)
+{
+    const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
+    if (q && (lane & 15u) == 0u)
+        q[4 * i + (lane >> 4)] = qa;
+    if (lane == 0u) {
+        actions[i] = (int8_t)r48::nt_argmax4(q0, q1, q2, q3);
+        if (legal)
+            legal[i] = (uint8_t)lg;
+    }
+}
+
+// The depth-2 search of a board that every lane of the wave holds (the lane mapping above): the
 // lane's Q_2 of its row's move (-inf where the move is illegal) and the board's legal set. Shared
 // by k_nt_search<L, 2>, whose board is the batch's, and k_nt_search3, whose boards are the root's
 // children.
@@ -347,12 +360,8 @@ __device__ __forceinline__ float nt_wave_q2(const r48::Board &b, uint32_t lane, 
     const float two0 = __shfl(leaf0, src), four0 = __shfl(leaf0, src + 1);
     const float two1 = __shfl(leaf1, src), four1 = __shfl(leaf1, src + 1);
     const bool late = rank2 >= 64u;
-    float x = slot ? r48::nt_fma(9.0f, late ? two1 : two0, late ? four1 : four0) : 0.0f;
-    x += __shfl_xor(x, 1);
-    x += __shfl_xor(x, 2);
-    x += __shfl_xor(x, 4);
-    x += __shfl_xor(x, 8);
-    return ok ? r48::nt_q2(r, x, r48::blanks(s).n) : -__builtin_inff();
+    const float x = slot ? r48::nt_fma(9.0f, late ? two1 : two0, late ? four1 : four0) : 0.0f;
+    return nt_row_q(x, ok, r, s);
 }
 
 template <int L, int DEPTH>
@@ -380,14 +389,7 @@ __global__ __launch_bounds__(kBlock) void k_nt_search(const int8_t *__restrict__
     } else {
         qa = nt_wave_q2<L>(b, lane, lay, tables, lg);
     }
-    const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
-    if (q && c == 0u)
-        q[4 * i + a] = qa;
-    if (lane == 0u) {
-        actions[i] = (int8_t)r48::nt_argmax4(q0, q1, q2, q3);
-        if (legal)
-            legal[i] = (uint8_t)lg;
-    }
+    nt_write_search(qa, lane, lg, i, actions, q, legal);
 }
 
 // The 3-ply search of r48_ntuple.h: a depth-2 search (nt_wave_q2) of each of the root's 2 to 120
@@ -511,40 +513,62 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restr
     float x = 0.0f;
     if (slot)   // rank2 + 1 < kids <= 120
         x = r48::nt_fma(9.0f, leaf[rank2], leaf[rank2 + 1u]);
-    x += __shfl_xor(x, 1);
-    x += __shfl_xor(x, 2);
-    x += __shfl_xor(x, 4);
-    x += __shfl_xor(x, 8);
-    const float qa = ok ? r48::nt_q2(r, x, r48::blanks(s).n) : -__builtin_inff();
-    const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
-    if (q && c == 0u)
-        q[4 * i + a] = qa;
-    if (lane == 0u) {
-        actions[i] = (int8_t)r48::nt_argmax4(q0, q1, q2, q3);
-        if (legal)
-            legal[i] = (uint8_t)lg;
-    }
+    nt_write_search(nt_row_q(x, ok, r, s), lane, lg, i, actions, q, legal);
 }
 
-// the arguments every entry point shares: boards, n, the layout
-int check_common(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
-                 r48::NtLayout &lay)
+// ---- the entry points ---------------------------------------------------------------------------
+
+// one pointer argument of an entry point: its name in the message, the alignment it needs, and
+// whether it may be NULL
+struct PtrArg {
+    const char *name;
+    const void *p;
+    uintptr_t align;
+    bool required;
+};
+
+// What every entry point checks first, in this order: boards and n, the layout (expanded into
+// lay), then the pointers as listed. R48_OK, or R48_EINVAL with the message set.
+int check_args(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+               r48::NtLayout &lay, std::initializer_list<PtrArg> ptrs)
 {
     if (!boards || !aligned(boards, 16) || n < 0)
         return fail(R48_EINVAL, std::string(fn) + ": boards NULL or not 16-byte aligned, or n < 0");
     if (const char *why = r48::nt_expand(cells, m, L, lay))
         return fail(R48_EINVAL, std::string(fn) + ": bad layout: " + why);
+    for (const PtrArg &a : ptrs) {
+        if (!a.p && a.required)
+            return fail(R48_EINVAL, std::string(fn) + ": " + a.name + " is NULL");
+        if (!aligned(a.p, a.align))
+            return fail(R48_EINVAL, std::string(fn) + ": " + a.name + " is not " + std::to_string(a.align) + "-byte aligned");
+    }
     return R48_OK;
 }
 
-#define R48_NT_DISPATCH(KERNEL, ...)                                                                       \
-    switch (lay.L) {                                                                                       \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-    case 3: hipLaunchKernelGGL(KERNEL<3>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-    case 5: hipLaunchKernelGGL(KERNEL<5>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(KERNEL<6>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); break; \
+// What follows the checks: nothing for n == 0, else f(std::integral_constant<int, L>()) launches
+// the instantiation for the layout's tuple length.
+template <class F>
+int run(const char *what, int64_t n, int L, F f)
+{
+    if (n == 0)
+        return R48_OK;
+    switch (L) {
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 5: f(std::integral_constant<int, 5>()); break;
+    default: f(std::integral_constant<int, 6>()); break;
     }
+    return launched(what);
+}
+
+template <class Kernel, class... A>
+void launch(Kernel kernel, dim3 grid, dim3 block, void *stream, const A &...args)
+{
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, args...);
+}
+
+unsigned long long *words(int64_t *acc) { return reinterpret_cast<unsigned long long *>(acc); }
 
 }  // namespace
 
@@ -554,29 +578,25 @@ int r48_ntuple_value(const int8_t *boards, int64_t n, const uint8_t *cells, int3
                      float *value, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_common("r48_ntuple_value", boards, n, cells, m, L, lay))
+    if (const int rc = check_args("r48_ntuple_value", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"value", value, 4, true}}))
         return rc;
-    if (!tables || !value || !aligned(tables, 4) || !aligned(value, 4))
-        return fail(R48_EINVAL, "r48_ntuple_value: tables/value NULL or not 4-byte aligned");
-    if (n == 0)
-        return R48_OK;
-    R48_NT_DISPATCH(k_nt_value, boards, n, lay, tables, value)
-    return launched("k_nt_value");
+    return run("k_nt_value", n, lay.L, [&](auto len) {
+        launch(k_nt_value<len()>, grid_for(n), kBlock, stream, boards, n, lay, tables, value);
+    });
 }
 
 int r48_ntuple_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
                    int8_t *actions, int8_t *after, float *value, int32_t *reward, uint8_t *legal, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_common("r48_ntuple_act", boards, n, cells, m, L, lay))
+    if (const int rc = check_args("r48_ntuple_act", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"actions", actions, 1, true}, {"after", after, 16, false},
+                                   {"value", value, 4, false}, {"reward", reward, 4, false}}))
         return rc;
-    if (!tables || !actions || !aligned(tables, 4) || !aligned(after, 16) || !aligned(value, 4) || !aligned(reward, 4))
-        return fail(R48_EINVAL, "r48_ntuple_act: tables/actions NULL, after not 16-byte aligned, or tables / value / "
-                                "reward not 4-byte aligned");
-    if (n == 0)
-        return R48_OK;
-    R48_NT_DISPATCH(k_nt_act, boards, n, lay, tables, actions, after, value, reward, legal)
-    return launched("k_nt_act");
+    return run("k_nt_act", n, lay.L, [&](auto len) {
+        launch(k_nt_act<len()>, grid_for(n), kBlock, stream, boards, n, lay, tables, actions, after, value, reward, legal);
+    });
 }
 
 int r48_ntuple_td_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
@@ -585,126 +605,88 @@ int r48_ntuple_td_act(const int8_t *boards, int64_t n, const uint8_t *cells, int
                       uint8_t *legal, uint8_t *valid_out, float *delta_out, int64_t *acc, uint32_t *cnt, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_common("r48_ntuple_td_act", boards, n, cells, m, L, lay))
+    if (const int rc = check_args("r48_ntuple_td_act", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"prev_after", prev_after, 16, true},
+                                   {"prev_value", prev_value, 4, true}, {"prev_done", prev_done, 1, true},
+                                   {"prev_valid", prev_valid, 1, true}, {"actions", actions, 1, true},
+                                   {"after", after, 16, true}, {"value", value, 4, true}, {"reward", reward, 4, false},
+                                   {"legal", legal, 1, true}, {"valid_out", valid_out, 1, true},
+                                   {"delta_out", delta_out, 4, false}, {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
         return rc;
-    if (!tables || !prev_after || !prev_value || !prev_done || !prev_valid || !actions || !after || !value || !legal ||
-        !valid_out || !acc || !cnt)
-        return fail(R48_EINVAL, "r48_ntuple_td_act: tables, prev_after / prev_value / prev_done / prev_valid, actions, "
-                                "after, value, legal, valid_out, acc or cnt NULL (only reward and delta_out may be)");
-    if (!aligned(prev_after, 16) || !aligned(after, 16) || !aligned(acc, 8) || !aligned(tables, 4) ||
-        !aligned(prev_value, 4) || !aligned(value, 4) || !aligned(reward, 4) || !aligned(delta_out, 4) || !aligned(cnt, 4))
-        return fail(R48_EINVAL, "r48_ntuple_td_act: prev_after / after not 16-byte aligned, acc not 8-byte aligned, or "
-                                "tables / prev_value / value / reward / delta_out / cnt not 4-byte aligned");
     if (after == prev_after || value == prev_value || valid_out == prev_valid)
         return fail(R48_EINVAL, "r48_ntuple_td_act: after, value and valid_out must not be the prev_ buffers (apply "
                                 "reads the previous afterstates and flags after this call; swap the buffers then)");
-    if (n == 0)
-        return R48_OK;
-    R48_NT_DISPATCH(k_nt_td_act, boards, n, lay, tables, prev_after, prev_value, prev_done, prev_valid, actions, after,
-                    value, reward, legal, valid_out, delta_out, reinterpret_cast<unsigned long long *>(acc), cnt)
-    return launched("k_nt_td_act");
+    return run("k_nt_td_act", n, lay.L, [&](auto len) {
+        launch(k_nt_td_act<len()>, grid_for(n), kBlock, stream, boards, n, lay, tables, prev_after, prev_value, prev_done,
+               prev_valid, actions, after, value, reward, legal, valid_out, delta_out, words(acc), cnt);
+    });
 }
 
 int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
                       int32_t depth, int8_t *actions, float *q, uint8_t *legal, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_common("r48_ntuple_search", boards, n, cells, m, L, lay))
+    if (const int rc = check_args("r48_ntuple_search", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"actions", actions, 1, true}, {"q", q, 4, false}}))
         return rc;
     if (depth != 1 && depth != 2)
         return fail(R48_EINVAL, "r48_ntuple_search: depth must be 1 or 2, got " + std::to_string(depth));
-    if (!tables || !actions || !aligned(tables, 4) || !aligned(q, 4))
-        return fail(R48_EINVAL, "r48_ntuple_search: tables/actions NULL, or tables / q not 4-byte aligned");
     const int64_t blocks = n / kSearchBoards + (n % kSearchBoards ? 1 : 0);   // one board per wave
     if (blocks > 0x7FFFFFFFll)
         return fail(R48_EINVAL, "r48_ntuple_search: n = " + std::to_string(n) + " boards exceed the grid (" +
                                     std::to_string(kSearchBoards) + " boards per workgroup, 2^31 - 1 workgroups)");
-    if (n == 0)
-        return R48_OK;
-    const dim3 grid((unsigned)blocks), block(kBlock);
-    const hipStream_t st = (hipStream_t)stream;
-#define R48_NT_SEARCH(LEN)                                                                                         \
-    case LEN:                                                                                                      \
-        if (depth == 1)                                                                                            \
-            hipLaunchKernelGGL((k_nt_search<LEN, 1>), grid, block, 0, st, boards, n, lay, tables, actions, q, legal); \
-        else                                                                                                       \
-            hipLaunchKernelGGL((k_nt_search<LEN, 2>), grid, block, 0, st, boards, n, lay, tables, actions, q, legal); \
-        break;
-    switch (lay.L) {
-        R48_NT_SEARCH(2)
-        R48_NT_SEARCH(3)
-        R48_NT_SEARCH(4)
-        R48_NT_SEARCH(5)
-        R48_NT_SEARCH(6)
-    }
-#undef R48_NT_SEARCH
-    return launched("k_nt_search");
+    const dim3 grid((unsigned)blocks);
+    return run("k_nt_search", n, lay.L, [&](auto len) {
+        if (depth == 1)
+            launch(k_nt_search<len(), 1>, grid, kBlock, stream, boards, n, lay, tables, actions, q, legal);
+        else
+            launch(k_nt_search<len(), 2>, grid, kBlock, stream, boards, n, lay, tables, actions, q, legal);
+    });
 }
 
 int r48_ntuple_search3(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
                        const float *tables, int8_t *actions, float *q, uint8_t *legal, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_common("r48_ntuple_search3", boards, n, cells, m, L, lay))
+    if (const int rc = check_args("r48_ntuple_search3", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"actions", actions, 1, true}, {"q", q, 4, false}}))
         return rc;
-    if (!tables || !actions || !aligned(tables, 4) || !aligned(q, 4))
-        return fail(R48_EINVAL, "r48_ntuple_search3: tables/actions NULL, or tables / q not 4-byte aligned");
     if (n > 0x7FFFFFFFll)   // one board per workgroup
         return fail(R48_EINVAL, "r48_ntuple_search3: n = " + std::to_string(n) +
                                     " boards exceed the grid (one per workgroup, 2^31 - 1 workgroups)");
-    if (n == 0)
-        return R48_OK;
     const dim3 grid((unsigned)n);
-    const hipStream_t st = (hipStream_t)stream;
-    const bool small = n <= kSearch3SmallBatch;
-#define R48_NT_SEARCH3(LEN)                                                                                          \
-    case LEN:                                                                                                        \
-        if (small)                                                                                                   \
-            hipLaunchKernelGGL((k_nt_search3<LEN, kSearch3WavesSmall>), grid, dim3(64 * kSearch3WavesSmall), 0, st,  \
-                               boards, n, lay, tables, actions, q, legal);                                           \
-        else                                                                                                         \
-            hipLaunchKernelGGL((k_nt_search3<LEN, kSearch3WavesLarge>), grid, dim3(64 * kSearch3WavesLarge), 0, st,  \
-                               boards, n, lay, tables, actions, q, legal);                                           \
-        break;
-    switch (lay.L) {
-        R48_NT_SEARCH3(2)
-        R48_NT_SEARCH3(3)
-        R48_NT_SEARCH3(4)
-        R48_NT_SEARCH3(5)
-        R48_NT_SEARCH3(6)
-    }
-#undef R48_NT_SEARCH3
-    return launched("k_nt_search3");
+    return run("k_nt_search3", n, lay.L, [&](auto len) {
+        if (n <= kSearch3SmallBatch)
+            launch(k_nt_search3<len(), kSearch3WavesSmall>, grid, 64 * kSearch3WavesSmall, stream, boards, n, lay, tables,
+                   actions, q, legal);
+        else
+            launch(k_nt_search3<len(), kSearch3WavesLarge>, grid, 64 * kSearch3WavesLarge, stream, boards, n, lay, tables,
+                   actions, q, legal);
+    });
 }
 
 int r48_ntuple_accumulate(const int8_t *boards, int64_t n, const float *delta, const uint8_t *valid,
                           const uint8_t *cells, int32_t m, int32_t L, int64_t *acc, uint32_t *cnt, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_common("r48_ntuple_accumulate", boards, n, cells, m, L, lay))
+    if (const int rc = check_args("r48_ntuple_accumulate", boards, n, cells, m, L, lay,
+                                  {{"delta", delta, 4, true}, {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
         return rc;
-    if (!delta || !acc || !cnt || !aligned(delta, 4) || !aligned(acc, 8) || !aligned(cnt, 4))
-        return fail(R48_EINVAL, "r48_ntuple_accumulate: delta/acc/cnt NULL, acc not 8-byte aligned, or delta / cnt "
-                                "not 4-byte aligned");
-    if (n == 0)
-        return R48_OK;
-    R48_NT_DISPATCH(k_nt_accumulate, boards, n, delta, valid, lay, reinterpret_cast<unsigned long long *>(acc), cnt)
-    return launched("k_nt_accumulate");
+    return run("k_nt_accumulate", n, lay.L, [&](auto len) {
+        launch(k_nt_accumulate<len()>, grid_for(n), kBlock, stream, boards, n, delta, valid, lay, words(acc), cnt);
+    });
 }
 
 int r48_ntuple_apply(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m, int32_t L,
                      float step, float *tables, int64_t *acc, uint32_t *cnt, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_common("r48_ntuple_apply", boards, n, cells, m, L, lay))
+    if (const int rc = check_args("r48_ntuple_apply", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
         return rc;
-    if (!tables || !acc || !cnt || !aligned(tables, 4) || !aligned(acc, 8) || !aligned(cnt, 4))
-        return fail(R48_EINVAL, "r48_ntuple_apply: tables/acc/cnt NULL, acc not 8-byte aligned, or tables / cnt not "
-                                "4-byte aligned");
-    if (n == 0)
-        return R48_OK;
-    R48_NT_DISPATCH(k_nt_apply, boards, n, valid, lay, step, tables, reinterpret_cast<unsigned long long *>(acc), cnt)
-    return launched("k_nt_apply");
+    return run("k_nt_apply", n, lay.L, [&](auto len) {
+        launch(k_nt_apply<len()>, grid_for(n), kBlock, stream, boards, n, valid, lay, step, tables, words(acc), cnt);
+    });
 }
 
 int r48_ntuple_apply_tc(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
@@ -712,31 +694,26 @@ int r48_ntuple_apply_tc(const int8_t *boards, int64_t n, const uint8_t *valid, c
                         void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_common("r48_ntuple_apply_tc", boards, n, cells, m, L, lay))
+    if (const int rc = check_args("r48_ntuple_apply_tc", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"tc_e", tc_e, 4, true}, {"tc_a", tc_a, 4, true},
+                                   {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
         return rc;
-    if (!tables || !tc_e || !tc_a || !acc || !cnt || !aligned(tables, 4) || !aligned(tc_e, 4) || !aligned(tc_a, 4) ||
-        !aligned(acc, 8) || !aligned(cnt, 4))
-        return fail(R48_EINVAL, "r48_ntuple_apply_tc: tables/tc_e/tc_a/acc/cnt NULL, acc not 8-byte aligned, or "
-                                "tables / tc_e / tc_a / cnt not 4-byte aligned");
-    if (n == 0)
-        return R48_OK;
-    R48_NT_DISPATCH(k_nt_apply_tc, boards, n, valid, lay, step, tables, tc_e, tc_a,
-                    reinterpret_cast<unsigned long long *>(acc), cnt)
-    return launched("k_nt_apply_tc");
+    return run("k_nt_apply_tc", n, lay.L, [&](auto len) {
+        launch(k_nt_apply_tc<len()>, grid_for(n), kBlock, stream, boards, n, valid, lay, step, tables, tc_e, tc_a,
+               words(acc), cnt);
+    });
 }
 
 int r48_ntuple_tc_rate(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tc_e,
                        const float *tc_a, float *rate_out, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_common("r48_ntuple_tc_rate", boards, n, cells, m, L, lay))
+    if (const int rc = check_args("r48_ntuple_tc_rate", boards, n, cells, m, L, lay,
+                                  {{"tc_e", tc_e, 4, true}, {"tc_a", tc_a, 4, true}, {"rate_out", rate_out, 4, true}}))
         return rc;
-    if (!tc_e || !tc_a || !rate_out || !aligned(tc_e, 4) || !aligned(tc_a, 4) || !aligned(rate_out, 4))
-        return fail(R48_EINVAL, "r48_ntuple_tc_rate: tc_e/tc_a/rate_out NULL or not 4-byte aligned");
-    if (n == 0)
-        return R48_OK;
-    R48_NT_DISPATCH(k_nt_tc_rate, boards, n, lay, tc_e, tc_a, rate_out)
-    return launched("k_nt_tc_rate");
+    return run("k_nt_tc_rate", n, lay.L, [&](auto len) {
+        launch(k_nt_tc_rate<len()>, grid_for(n), kBlock, stream, boards, n, lay, tc_e, tc_a, rate_out);
+    });
 }
 
 }  // extern "C"

@@ -50,6 +50,18 @@ def layout_cells(layout):
     return cells
 
 
+# the outputs of act, td_act and the searches: (name, dtype, shape after [n])
+_ACT_OUT = (("actions", torch.int8, ()), ("after", torch.int8, (16,)), ("value", torch.float32, ()),
+            ("reward", torch.int32, ()), ("legal", torch.uint8, ()))
+_TD_ACT_OUT = _ACT_OUT + (("valid", torch.uint8, ()), ("delta", torch.float32, ()))
+_SEARCH_OUT = (("actions", torch.int8, ()), ("q", torch.float32, (4,)), ("legal", torch.uint8, ()))
+
+
+def _outs(spec, given, n, boards):
+    """The output tensors of one call in the order of `spec`: the given ones checked, the rest allocated."""
+    return tuple(_out(t, name, dtype, (n,) + tail, boards) for t, (name, dtype, tail) in zip(given, spec))
+
+
 class NTupleNet:
     """The tables float32 [m, 16^L] and the update's scratch (acc int64, cnt uint32 held as int32,
     same shape; zero between calls) on one GPU. With tc, also the error sums tc_e and tc_a of the
@@ -88,14 +100,9 @@ class NTupleNet:
         reward + V(afterstate), ties to the lowest code. No legal move: action 0, the board itself,
         value 0, reward 0, legal 0."""
         n = _boards(boards)
-        actions = _out(actions, "actions", torch.int8, (n,), boards)
-        after = _out(after, "after", torch.int8, (n, 16), boards)
-        value = _out(value, "value", torch.float32, (n,), boards)
-        reward = _out(reward, "reward", torch.int32, (n,), boards)
-        legal = _out(legal, "legal", torch.uint8, (n,), boards)
-        check(self._lib.r48_ntuple_act(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(actions), ptr(after),
-                                       ptr(value), ptr(reward), ptr(legal), _stream(boards)))
-        return actions, after, value, reward, legal
+        outs = _outs(_ACT_OUT, (actions, after, value, reward, legal), n, boards)
+        check(self._lib.r48_ntuple_act(ptr(boards), n, *self._lay(), ptr(self.tables), *map(ptr, outs), _stream(boards)))
+        return outs
 
     def td_act(self, boards, prev_after, prev_value, prev_done, prev_valid, actions=None, after=None, value=None,
                reward=None, legal=None, valid=None, delta=None):
@@ -112,18 +119,11 @@ class NTupleNet:
                                (prev_valid, "prev_valid", torch.uint8)):
             if _dev(t, name, dtype).numel() != n:
                 raise ValueError("%s must have one element per board (%d)" % (name, n))
-        actions = _out(actions, "actions", torch.int8, (n,), boards)
-        after = _out(after, "after", torch.int8, (n, 16), boards)
-        value = _out(value, "value", torch.float32, (n,), boards)
-        reward = _out(reward, "reward", torch.int32, (n,), boards)
-        legal = _out(legal, "legal", torch.uint8, (n,), boards)
-        valid = _out(valid, "valid", torch.uint8, (n,), boards)
-        delta = _out(delta, "delta", torch.float32, (n,), boards)
+        outs = _outs(_TD_ACT_OUT, (actions, after, value, reward, legal, valid, delta), n, boards)
         check(self._lib.r48_ntuple_td_act(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(prev_after),
-                                          ptr(prev_value), ptr(prev_done), ptr(prev_valid), ptr(actions), ptr(after),
-                                          ptr(value), ptr(reward), ptr(legal), ptr(valid), ptr(delta), ptr(self.acc),
-                                          ptr(self.cnt), _stream(boards)))
-        return actions, after, value, reward, legal, valid, delta
+                                          ptr(prev_value), ptr(prev_done), ptr(prev_valid), *map(ptr, outs),
+                                          ptr(self.acc), ptr(self.cnt), _stream(boards)))
+        return outs
 
     def accumulate(self, boards, delta, valid=None):
         """First half of td_update: per-entry hit counts and fixed-point delta sums into the scratch."""
@@ -175,12 +175,10 @@ class NTupleNet:
         if depth not in (1, 2):
             raise ValueError("search depth is 1 or 2, got %r (three plies: search3)" % (depth,))
         n = _boards(boards)
-        actions = _out(actions, "actions", torch.int8, (n,), boards)
-        q = _out(q, "q", torch.float32, (n, 4), boards)
-        legal = _out(legal, "legal", torch.uint8, (n,), boards)
-        check(self._lib.r48_ntuple_search(ptr(boards), n, *self._lay(), ptr(self.tables), depth, ptr(actions), ptr(q),
-                                          ptr(legal), _stream(boards)))
-        return actions, q, legal
+        outs = _outs(_SEARCH_OUT, (actions, q, legal), n, boards)
+        check(self._lib.r48_ntuple_search(ptr(boards), n, *self._lay(), ptr(self.tables), depth, *map(ptr, outs),
+                                          _stream(boards)))
+        return outs
 
     def search3(self, boards, actions=None, q=None, legal=None):
         """The 3-ply expectimax search -> (actions int8 [n], q float32 [n, 4], legal uint8 [n]):
@@ -190,12 +188,10 @@ class NTupleNet:
         One kernel, one board per workgroup: a depth-2 search of each of the board's 2 to 120
         children."""
         n = _boards(boards)
-        actions = _out(actions, "actions", torch.int8, (n,), boards)
-        q = _out(q, "q", torch.float32, (n, 4), boards)
-        legal = _out(legal, "legal", torch.uint8, (n,), boards)
-        check(self._lib.r48_ntuple_search3(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(actions), ptr(q),
-                                           ptr(legal), _stream(boards)))
-        return actions, q, legal
+        outs = _outs(_SEARCH_OUT, (actions, q, legal), n, boards)
+        check(self._lib.r48_ntuple_search3(ptr(boards), n, *self._lay(), ptr(self.tables), *map(ptr, outs),
+                                           _stream(boards)))
+        return outs
 
     def policy(self, depth=1):
         """`policy(boards, t) -> actions` for evaluate.play_episodes: the fused greedy search (depth
@@ -291,20 +287,18 @@ class NTupleTrainer:
                        self.after, self.value, self.reward, self.legal, self.valid, self.delta)
             net.apply(self.prev_after, self.cfg.alpha / (8.0 * net.m), self.prev_valid)
             env.step(self.actions, auto_reset=True, done_out=self.prev_done)
-            self.after, self.prev_after = self.prev_after, self.after
-            self.value, self.prev_value = self.prev_value, self.value
             self.valid, self.prev_valid = self.prev_valid, self.valid
-            self.updates += 1
-            return
-        net.act(env.boards, self.actions, self.after, self.value, self.reward, self.legal)
-        target = torch.where(self.prev_done != 0, torch.zeros_like(self.value), self.reward.float() + self.value)
-        torch.sub(target, self.prev_value, out=self.delta)
-        net.td_update(self.prev_after, self.delta, self.cfg.alpha, self.prev_valid)
-        _, _, done = env.step(self.actions, auto_reset=True)
+        else:
+            net.act(env.boards, self.actions, self.after, self.value, self.reward, self.legal)
+            target = torch.where(self.prev_done != 0, torch.zeros_like(self.value), self.reward.float() + self.value)
+            torch.sub(target, self.prev_value, out=self.delta)
+            net.td_update(self.prev_after, self.delta, self.cfg.alpha, self.prev_valid)
+            _, _, done = env.step(self.actions, auto_reset=True)
+            self.prev_done.copy_(done)
+            self.prev_valid.copy_(self.legal != 0)   # an afterstate exists where a move did
+        # this step's afterstates and values become the previous ones
         self.after, self.prev_after = self.prev_after, self.after
         self.value, self.prev_value = self.prev_value, self.value
-        self.prev_done.copy_(done)
-        self.prev_valid.copy_(self.legal != 0)   # an afterstate exists where a move did
         self.updates += 1
 
     def train_steps(self, k):

@@ -1,77 +1,22 @@
 // Host build of the n-tuple network's layout expansion, entry index and value sum
-// (rein48_amd/csrc/r48_ntuple.h) checked against a naive restatement written here: eight explicit
-// board transforms, the index cell by cell -- a CPU test harness, never shipped. Build+run:
+// (rein48_amd/csrc/r48_ntuple.h) checked against the naive restatement of ntuple_naive.h: eight
+// explicit board transforms, the index cell by cell -- a CPU test harness, never shipped. Build+run:
 // tests/test_ntuple_host.py (g++ -O2).
 #include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <random>
-#include <vector>
 
 #include "../../rein48_amd/csrc/r48_ntuple.h"
+#include "ntuple_naive.h"
 
 using r48::Board;
-
-static int fails = 0;
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        if (!(cond)) {                                    \
-            if (fails < 20) {                             \
-                fprintf(stderr, "FAIL %s:%d ", __FILE__, __LINE__); \
-                fprintf(stderr, __VA_ARGS__);             \
-                fprintf(stderr, "\n");                    \
-            }                                             \
-            fails++;                                      \
-        }                                                 \
-    } while (0)
-
-static Board load(const int8_t *b)
-{
-    Board r;
-    memcpy(&r, b, 16);
-    return r;
-}
-
-// ---- the naive restatement ------------------------------------------------------------------
-// the eight symmetries of the square as explicit transforms of a 4x4 grid: out[r][c] = ...
-static void transform(int which, const int8_t *in, int8_t *out)
-{
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) {
-            int sr, sc;
-            switch (which) {
-            case 0: sr = r; sc = c; break;              // identity
-            case 1: sr = 3 - c; sc = r; break;          // quarter turn
-            case 2: sr = 3 - r; sc = 3 - c; break;      // half turn
-            case 3: sr = c; sc = 3 - r; break;          // three quarter turn
-            case 4: sr = r; sc = 3 - c; break;          // mirror left-right
-            case 5: sr = 3 - r; sc = c; break;          // mirror top-bottom
-            case 6: sr = c; sc = r; break;              // main diagonal
-            default: sr = 3 - c; sc = 3 - r; break;     // anti-diagonal
-            }
-            out[4 * r + c] = in[4 * sr + sc];
-        }
-}
-
-static uint32_t naive_index(const int8_t *b, const uint8_t *tuple, int L)
-{
-    uint32_t idx = 0, scale = 1;
-    for (int k = 0; k < L; k++) {
-        const int e = b[tuple[k]] < 15 ? b[tuple[k]] : 15;
-        idx += (uint32_t)e * scale;
-        scale *= 16;
-    }
-    return idx;
-}
 
 // the 8 indices of tuple t on board b, sorted (the enumeration order of the symmetries is free)
 static void naive_hits(const int8_t *b, const uint8_t *tuple, int L, uint32_t out[8])
 {
     for (int g = 0; g < 8; g++) {
-        int8_t tb[16];
-        transform(g, b, tb);
-        out[g] = naive_index(tb, tuple, L);
+        Grid tb;
+        transform(g, grid_of(b), tb);
+        out[g] = (uint32_t)naive_index(tb, tuple, L);
     }
     std::sort(out, out + 8);
 }
@@ -87,21 +32,6 @@ static void header_hits(const Board &b, const r48::NtLayout &lay, int t, uint32_
     }
     std::sort(out, out + 8);
 }
-
-struct Layout {
-    const char *name;
-    int m, L;
-    uint8_t cells[48];
-};
-
-static const Layout kLayouts[] = {
-    {"lines-squares", 5, 4, {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 4, 5, 1, 2, 5, 6, 5, 6, 9, 10}},
-    {"4x6", 4, 6, {0, 1, 2, 3, 4, 5, 4, 5, 6, 7, 8, 9, 0, 1, 2, 4, 5, 6, 4, 5, 6, 8, 9, 10}},
-    {"3x3", 3, 3, {0, 1, 2, 5, 9, 10, 15, 3, 12}},
-    {"1x2", 1, 2, {7, 8}},
-    {"8x5", 8, 5, {0, 1, 2, 3, 4,  5, 6, 7, 8, 9,  10, 11, 12, 13, 14,  15, 0, 5, 10, 3,
-                   12, 9, 6, 3, 0,  1, 4, 2, 8, 15,  14, 13, 11, 7, 2,  6, 10, 14, 12, 4}},
-};
 
 // integer tables in [-1024, 1024]: any summation order is exact in fp32
 static std::vector<float> int_tables(int m, int L, uint64_t seed)
@@ -202,13 +132,13 @@ static void run_layout(const Layout &ly)
 
 int main()
 {
-    for (const Layout &ly : kLayouts) {
-        switch (ly.L) {
-        case 2: run_layout<2>(ly); break;
-        case 3: run_layout<3>(ly); break;
-        case 4: run_layout<4>(ly); break;
-        case 5: run_layout<5>(ly); break;
-        default: run_layout<6>(ly); break;
+    for (const Layout *ly : {&kLinesSquares, &k4x6, &k3x3, &k1x2, &k8x5}) {
+        switch (ly->L) {
+        case 2: run_layout<2>(*ly); break;
+        case 3: run_layout<3>(*ly); break;
+        case 4: run_layout<4>(*ly); break;
+        case 5: run_layout<5>(*ly); break;
+        default: run_layout<6>(*ly); break;
         }
     }
     // the eight placed symmetries are eight different maps of the cells, each a bijection

@@ -1,6 +1,6 @@
 // Host build of the n-tuple network's per-board search at depth 3 (rein48_amd/csrc/r48_ntuple.h:
 // nt_search_board, nt_best, nt_q_level -- the contract k_nt_search3 shares) checked against a naive
-// restatement written here: explicit 4x4 arrays, its own line-by-line move, eight explicit board
+// restatement (ntuple_naive.h and here): explicit 4x4 arrays, its own line-by-line move, eight explicit board
 // transforms for the value, plain recursion over the plies, float64 throughout -- a CPU test
 // harness, never shipped. Build+run: tests/test_ntuple_search3_host.py (g++ -O2).
 //
@@ -18,147 +18,12 @@
 //     the last factor for the products of the level's chained roundings (at most ~130).
 // Depth 3 applies the level twice. Legal sets are exact; q is within err; the action is legal and
 // its float64 Q is within err[action] + err[a'] of every other legal move's.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <random>
-#include <vector>
 
 #include "../../rein48_amd/csrc/r48_ntuple.h"
+#include "ntuple_naive.h"
 
 using r48::Board;
-
-static int fails = 0;
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        if (!(cond)) {                                    \
-            if (fails < 20) {                             \
-                fprintf(stderr, "FAIL %s:%d ", __FILE__, __LINE__); \
-                fprintf(stderr, __VA_ARGS__);             \
-                fprintf(stderr, "\n");                    \
-            }                                             \
-            fails++;                                      \
-        }                                                 \
-    } while (0)
-
-static Board load(const int8_t *b)
-{
-    Board r;
-    memcpy(&r, b, 16);
-    return r;
-}
-
-// ---- the naive restatement ------------------------------------------------------------------
-struct Grid {
-    int g[4][4];
-};
-
-static Grid grid_of(const int8_t *b)
-{
-    Grid x;
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++)
-            x.g[r][c] = b[4 * r + c];
-    return x;
-}
-
-// one line toward index 0: drop the blanks, merge equal neighbours once from the wall outwards
-static long move_line(int line[4])
-{
-    int t[4], k = 0;
-    long reward = 0;
-    for (int i = 0; i < 4; i++)
-        if (line[i])
-            t[k++] = line[i];
-    int out[4] = {0, 0, 0, 0}, o = 0;
-    for (int i = 0; i < k; i++) {
-        if (i + 1 < k && t[i] == t[i + 1]) {
-            out[o++] = t[i] + 1;
-            reward += 1L << (t[i] + 1);
-            i++;
-        } else {
-            out[o++] = t[i];
-        }
-    }
-    for (int i = 0; i < 4; i++)
-        line[i] = out[i];
-    return reward;
-}
-
-// action 0 UP, 1 DOWN, 2 LEFT, 3 RIGHT; returns whether the grid changed
-static bool naive_move(const Grid &in, int a, Grid &out, long &reward)
-{
-    out = in;
-    reward = 0;
-    for (int l = 0; l < 4; l++) {
-        int line[4];
-        for (int k = 0; k < 4; k++) {
-            const int j = (a & 1) ? 3 - k : k;   // DOWN / RIGHT: counted from the far wall
-            line[k] = a < 2 ? in.g[j][l] : in.g[l][j];
-        }
-        reward += move_line(line);
-        for (int k = 0; k < 4; k++) {
-            const int j = (a & 1) ? 3 - k : k;
-            (a < 2 ? out.g[j][l] : out.g[l][j]) = line[k];
-        }
-    }
-    return memcmp(&in, &out, sizeof in) != 0;
-}
-
-struct Layout {
-    const char *name;
-    int m, L;
-    uint8_t cells[48];
-};
-
-static const Layout kLayouts[] = {
-    {"3x3", 3, 3, {0, 1, 2, 5, 9, 10, 15, 3, 12}},
-    {"lines-squares", 5, 4, {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 4, 5, 1, 2, 5, 6, 5, 6, 9, 10}},
-};
-
-static void transform(int which, const Grid &in, Grid &out)
-{
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) {
-            int sr, sc;
-            switch (which) {
-            case 0: sr = r; sc = c; break;
-            case 1: sr = 3 - c; sc = r; break;
-            case 2: sr = 3 - r; sc = 3 - c; break;
-            case 3: sr = c; sc = 3 - r; break;
-            case 4: sr = r; sc = 3 - c; break;
-            case 5: sr = 3 - r; sc = c; break;
-            case 6: sr = c; sc = r; break;
-            default: sr = 3 - c; sc = 3 - r; break;
-            }
-            out.g[r][c] = in.g[sr][sc];
-        }
-}
-
-// V and the sum of its hits' magnitudes
-static double naive_value(const Layout &ly, const std::vector<float> &tables, const Grid &b, double &habs)
-{
-    double v = 0.0;
-    habs = 0.0;
-    for (int g = 0; g < 8; g++) {
-        Grid t;
-        transform(g, b, t);
-        for (int k = 0; k < ly.m; k++) {
-            size_t idx = 0, scale = 1;
-            for (int j = 0; j < ly.L; j++) {
-                const int cell = ly.cells[k * ly.L + j];
-                const int e = t.g[cell >> 2][cell & 3];
-                idx += (size_t)(e < 15 ? e : 15) * scale;
-                scale *= 16;
-            }
-            const double h = tables[((size_t)k << (4 * ly.L)) + idx];
-            v += h;
-            habs += std::fabs(h);
-        }
-    }
-    return v;
-}
 
 static int blanks_of(const Grid &b)
 {
@@ -216,7 +81,7 @@ struct Naive {
             return q_level(after, r, k);
         double habs;
         Est q;
-        q.val = r + naive_value(ly, tables, after, habs);
+        q.val = r + naive_value(ly, tables, after, &habs);
         q.mag = std::fabs(r) + habs;
         q.err = 8.0 * ly.m * U * habs + U * q.mag;
         return q;
@@ -386,12 +251,12 @@ static void run_layout(const Layout &ly, bool integer, long n_random)
 
 int main()
 {
-    for (const Layout &ly : kLayouts)
+    for (const Layout *ly : {&k3x3, &kLinesSquares})
         for (int integer = 0; integer <= 1; integer++) {
-            if (ly.L == 3)
-                run_layout<3>(ly, integer != 0, 40);
+            if (ly->L == 3)
+                run_layout<3>(*ly, integer != 0, 40);
             else
-                run_layout<4>(ly, integer != 0, 40);
+                run_layout<4>(*ly, integer != 0, 40);
         }
     printf("ntuple_search3_test: %s (%d failures)\n", fails ? "FAIL" : "OK", fails);
     return fails ? 1 : 0;

@@ -1,34 +1,10 @@
 // Host build of the temporal-coherence rule of rein48_amd/csrc/r48_ntuple.h (nt_mean, nt_tc_rate,
 // nt_tc_update, nt_tc_rate_mean) checked against a naive double-precision restatement written
 // here -- a CPU test harness, never shipped. Build+run: tests/test_ntuple_tc_host.py (g++ -O2).
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <random>
-#include <vector>
 
 #include "../../rein48_amd/csrc/r48_ntuple.h"
-
-static int fails = 0;
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        if (!(cond)) {                                    \
-            if (fails < 20) {                             \
-                fprintf(stderr, "FAIL %s:%d ", __FILE__, __LINE__); \
-                fprintf(stderr, __VA_ARGS__);             \
-                fprintf(stderr, "\n");                    \
-            }                                             \
-            fails++;                                      \
-        }                                                 \
-    } while (0)
-
-static uint32_t bits(float x)
-{
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
+#include "ntuple_naive.h"
 
 // ---- the naive restatement, in double ---------------------------------------------------------
 struct Naive {
