@@ -657,6 +657,29 @@ int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int
 int r48_ntuple_search3(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
                        const float *tables, int8_t *actions, float *q, uint8_t *legal, void *stream);
 
+/* Whole games in one launch: search and env step for n_steps steps, every board in registers from
+ * its load to its store. For t = 0 .. n_steps - 1, board i
+ *   1. takes the action r48_ntuple_act returns for it (depth 1) or r48_ntuple_search(depth = 2)
+ *      (depth 2), then
+ *   2. makes exactly the step r48_env_step(actions, flags = 0) makes on an env with seed env_seed,
+ *      global board id gid0 + i and step counter env_step + t (uint32, it wraps): draw contract 3.
+ *      No auto-reset.
+ * Stateless like r48_cnn_rollout: the caller advances the env's step counter by n_steps
+ * (r48_env_set_counters). boards int8[n][16] are updated in place. length int32[n] (nullable,
+ * in/out) += the number of steps that changed the board; gain int32[n] (nullable, in/out) += the
+ * sum of their merge rewards, so chunked calls add up; done uint8[n] (nullable) = has_game_over
+ * after the last step, as the last r48_env_step writes it. Everything equals n_steps x (act or
+ * search, then r48_env_step) bit for bit, for every n, gid0 and env_step. A board without a legal
+ * move is finished -- action 0 leaves it as it is -- so the kernel stops working on it, and a wave
+ * leaves its step loop once none of its boards is alive: a call costs a wave the moves of its
+ * longest game, not n_steps. R48_EINVAL (before any HIP call) as r48_ntuple_value, and for NULL
+ * tables, tables / length / gain not 4-byte aligned, depth not 1 or 2, n_steps < 0, or n beyond the
+ * grid (depth 2: 4 * (2^31 - 1) boards as r48_ntuple_search). n == 0 or n_steps == 0 is a no-op
+ * after these checks. */
+int r48_ntuple_play(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                    int32_t depth, int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step,
+                    int32_t *length, int32_t *gain, uint8_t *done, void *stream);
+
 /* The TD update in two launches, both over the hits (i, t, g) of the boards with valid[i] != 0
  * (valid NULL: all). Scratch: acc int64[m][16^L], cnt uint32[m][16^L], which MUST BE ALL ZERO ON
  * ENTRY to r48_ntuple_accumulate (r48_ntuple_apply leaves them zero again).

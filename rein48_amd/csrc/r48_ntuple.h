@@ -477,4 +477,49 @@ inline uint32_t nt_search_board(const Board &b, const NtLayout &lay, const float
     return nt_argmax4(q[0], q[1], q[2], q[3]);
 }
 
+// ---- playing whole games ----------------------------------------------------------------------
+// The play contract (k_nt_play1, k_nt_play2, and nt_play_board for one board on the host): for
+// t = 0 .. n_steps - 1 the board takes the search's action (depth 1: act's, depth 2: the search's)
+// and then the env's Philox-mode step with it (r48_env_step, flags 0: no auto-reset) as board
+// `gid` of an env with key (k0, k1) at step counter step0 + t (uint32, it wraps) -- draw contract
+// 3: step_draw's pair sharing, the rank over the blanks in the line order of the move,
+// kFourThresh30. A board without a legal move gets action 0, which leaves it as it is: it is
+// finished, and every later step is the identity on it. length counts the steps that changed the
+// board, gain sums their merge rewards, done is has_game_over after the last step -- a function of
+// the final board alone (game over is invariant under the board's symmetries), so a kernel that
+// stops stepping a finished board still writes the last step's done.
+
+// The env's step of one board after the action is chosen: the draw and step_board, stated once for
+// the kernels and the host.
+R48_HD StepOut nt_play_step(Board &b, uint32_t action, uint64_t gid, uint32_t step, uint32_t k0, uint32_t k1)
+{
+    uint32_t x, y;
+    step_draw(gid, step, k0, k1, x, y);
+    return step_board<true, false, true>(b, action, y, (x & 0x3FFFFFFFu) < kFourThresh30);
+}
+
+// done as the last step writes it, from the board that step left
+R48_HD uint32_t nt_play_done(const Board &b) { return game_over(b, blanks(b).n) ? 1u : 0u; }
+
+// The contract for one board, serially: n_steps x (nt_search_board, nt_play_step), every step made
+// whether the board is finished or not. length and gain are added to, done is written (each
+// nullable); n_steps == 0 touches nothing.
+template <int L>
+inline void nt_play_board(Board &board, const NtLayout &lay, const float *tables, int depth, int n_steps, uint32_t k0,
+                          uint32_t k1, uint64_t gid, uint32_t step0, int32_t *length, int32_t *gain, uint8_t *done)
+{
+    for (int t = 0; t < n_steps; t++) {
+        float q[4];
+        uint32_t legal;
+        const uint32_t action = nt_search_board<L>(board, lay, tables, depth, q, legal);
+        const StepOut o = nt_play_step(board, action, gid, step0 + (uint32_t)t, k0, k1);
+        if (length)
+            *length += (int32_t)o.changed;
+        if (gain)
+            *gain += (int32_t)o.reward;
+        if (done)
+            *done = (uint8_t)o.done;
+    }
+}
+
 }  // namespace r48

@@ -11,6 +11,8 @@
 //   nt_wave_q2       the depth-2 search of a board by a wave     k_nt_search<L, 2>, k_nt_search3
 //   nt_row_q,        how a search ends: butterfly, Q, the four   nt_wave_q2, k_nt_search,
 //   nt_write_search  rows' scores, argmax, the writes            k_nt_search3
+//   nt_play_store    what a played board leaves behind           k_nt_play1 (over nt_act_board),
+//                                                                k_nt_play2 (over nt_wave_q2)
 // and r48_ntuple.h's nt_value (k_nt_value and everything above) and nt_tc_rate_mean (k_nt_tc_rate).
 // k_nt_td_act is act, the trainer's TD error and accumulate for the previous step's afterstates in
 // one launch: the fused training step. k_nt_search runs one board per WAVE, k_nt_search3 one per
@@ -516,6 +518,137 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restr
     nt_write_search(nt_row_q(x, ok, r, s), lane, lg, i, actions, q, legal);
 }
 
+// ---- playing whole games: search and env step for n_steps steps in one launch -------------------
+// The play contract of r48_ntuple.h. A board stays in registers from its one load to its one store;
+// length and gain are summed in registers and added to the caller's words at the end. A board
+// without a legal move is finished: the contract's remaining steps are the identity on it, so its
+// lane stops searching (no gather is issued for it again) and a wave leaves the step loop once
+// none of its boards is alive -- a batch played to the end costs each wave the moves of its longest
+// game, not n_steps. Nothing is shared between boards: no barrier, no LDS, no atomics.
+
+// what a board's play leaves behind, written by one lane
+__device__ __forceinline__ void nt_play_store(int8_t *__restrict__ boards, int64_t i, const r48::Board &b, uint32_t len,
+                                              uint32_t gn, int32_t *__restrict__ length, int32_t *__restrict__ gain,
+                                              uint8_t *__restrict__ done)
+{
+    *reinterpret_cast<uint4 *>(boards + 16 * i) = make_uint4(b.w0, b.w1, b.w2, b.w3);
+    if (length)
+        length[i] += (int32_t)len;
+    if (gain)
+        gain[i] += (int32_t)gn;
+    if (done)
+        done[i] = (uint8_t)r48::nt_play_done(b);
+}
+
+// Depth 1, LANES lanes per board.
+//   LANES == 4 (what runs): lane 4 j + a of a wave holds board j like its three neighbours and
+//     scores move a alone (nt_score: nt_value's order); the four scores come back by __shfl and
+//     every lane takes act's first maximiser over the legal moves, then makes the same step. A
+//     board's dependent chain of gathers is a quarter as long and a batch is four times as many
+//     waves: 4,096 boards are 256 waves instead of 64 on 1,024 SIMDs.
+//   LANES == 1 (-DR48_NT_PLAY_LANES=1, an experiment's build): nt_act_board, act's search as it is.
+// Either way the bits are act's: the value sum is nt_value's, the winner the first legal move whose
+// score is strictly above every earlier legal one. Measured (DESIGN.md section 16,
+// profiles/ntuple/play_mapping_ab.log): four lanes take a third of the time per step at 4,096
+// boards and the same time at 2^16.
+#ifndef R48_NT_PLAY_LANES
+#define R48_NT_PLAY_LANES 4
+#endif
+constexpr int kPlayLanes = R48_NT_PLAY_LANES;
+
+template <int L, int LANES>
+__global__ __launch_bounds__(kBlock) void k_nt_play1(int8_t *__restrict__ boards, int64_t n, const r48::NtLayout lay,
+                                                     const float *__restrict__ tables, int32_t n_steps, uint32_t k0,
+                                                     uint32_t k1, int64_t gid0, uint32_t step0,
+                                                     int32_t *__restrict__ length, int32_t *__restrict__ gain,
+                                                     uint8_t *__restrict__ done)
+{
+    static_assert(LANES == 1 || LANES == 4, "one lane per board, or one per move");
+    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
+    if (i >= n)
+        return;   // with LANES == 4, all four lanes of the board
+    const uint32_t sub = threadIdx.x & (uint32_t)(LANES - 1);
+    const uint64_t gid = (uint64_t)(gid0 + i);
+    r48::Board b = r48::load_board(boards, i);
+    uint32_t len = 0u, gn = 0u;
+    bool alive = true;
+#pragma unroll 1
+    for (int32_t t = 0; t < n_steps; t++) {
+        if (__ballot(alive) == 0ull)
+            break;   // the whole wave is finished
+        if (alive) {
+            uint32_t action, lg;
+            if (LANES == 1) {
+                const NtMove mv = nt_act_board<L>(b, lay, tables);
+                action = mv.action;
+                lg = mv.legal;
+            } else {
+                const r48::Moves4 m = r48::move_rows4<true>(b);
+                lg = r48::nt_legal4(m, b);
+                float s = 0.0f;
+                if ((lg >> sub) & 1u)
+                    s = r48::nt_score<L>(r48::nt_pick(m, sub), r48::nt_pick_reward(m, sub), lay, tables);
+                const int first = (int)(threadIdx.x & 63u & ~3u);
+                action = 0u;
+                float best = 0.0f;
+                bool have = false;
+#pragma unroll
+                for (uint32_t a = 0; a < 4u; a++) {
+                    const float sa = __shfl(s, first + (int)a);
+                    if (((lg >> a) & 1u) && (!have || sa > best)) {
+                        have = true;
+                        best = sa;
+                        action = a;
+                    }
+                }
+            }
+            if (lg == 0u) {
+                alive = false;
+            } else {
+                const r48::StepOut o = r48::nt_play_step(b, action, gid, step0 + (uint32_t)t, k0, k1);
+                len += o.changed;
+                gn += o.reward;
+                alive = o.done == 0u;
+            }
+        }
+    }
+    if (sub == 0u)
+        nt_play_store(boards, i, b, len, gn, length, gain, done);
+}
+
+// Depth 2, one board per wave as k_nt_search<L, 2>: every lane holds the board, nt_wave_q2 searches
+// it, the rows' scores are read as nt_write_search reads them and every lane takes their first
+// maximiser and makes the same step, so the board stays wave-uniform; lane 0 stores it once at the
+// end.
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_play2(int8_t *__restrict__ boards, int64_t n, const r48::NtLayout lay,
+                                                     const float *__restrict__ tables, int32_t n_steps, uint32_t k0,
+                                                     uint32_t k1, int64_t gid0, uint32_t step0,
+                                                     int32_t *__restrict__ length, int32_t *__restrict__ gain,
+                                                     uint8_t *__restrict__ done)
+{
+    const int64_t i = (int64_t)blockIdx.x * kSearchBoards + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (i >= n)
+        return;   // the whole wave
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t gid = (uint64_t)(gid0 + i);
+    r48::Board b = r48::load_board(boards, i);
+    uint32_t len = 0u, gn = 0u;
+#pragma unroll 1
+    for (int32_t t = 0; t < n_steps; t++) {
+        uint32_t lg;
+        const float qa = nt_wave_q2<L>(b, lane, lay, tables, lg);
+        if (uniform_word(lg) == 0u)
+            break;   // finished: the wave leaves
+        const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
+        const r48::StepOut o = r48::nt_play_step(b, r48::nt_argmax4(q0, q1, q2, q3), gid, step0 + (uint32_t)t, k0, k1);
+        len += o.changed;
+        gn += o.reward;
+    }
+    if (lane == 0u)
+        nt_play_store(boards, i, b, len, gn, length, gain, done);
+}
+
 // ---- the entry points ---------------------------------------------------------------------------
 
 // one pointer argument of an entry point: its name in the message, the alignment it needs, and
@@ -662,6 +795,37 @@ int r48_ntuple_search3(const int8_t *boards, int64_t n, const uint8_t *cells, in
         else
             launch(k_nt_search3<len(), kSearch3WavesLarge>, grid, 64 * kSearch3WavesLarge, stream, boards, n, lay, tables,
                    actions, q, legal);
+    });
+}
+
+int r48_ntuple_play(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                    int32_t depth, int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step, int32_t *length,
+                    int32_t *gain, uint8_t *done, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_args("r48_ntuple_play", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"length", length, 4, false}, {"gain", gain, 4, false}}))
+        return rc;
+    if (depth != 1 && depth != 2)
+        return fail(R48_EINVAL, "r48_ntuple_play: depth must be 1 or 2, got " + std::to_string(depth));
+    if (n_steps < 0)
+        return fail(R48_EINVAL, "r48_ntuple_play: n_steps must not be negative, got " + std::to_string(n_steps));
+    const int64_t per = depth == 2 ? kSearchBoards : kBlock / kPlayLanes;   // boards per workgroup
+    const int64_t blocks = n / per + (n % per ? 1 : 0);
+    if (blocks > 0x7FFFFFFFll)
+        return fail(R48_EINVAL, "r48_ntuple_play: n = " + std::to_string(n) + " boards exceed the grid (" +
+                                    std::to_string(per) + " boards per workgroup, 2^31 - 1 workgroups)");
+    if (n_steps == 0)
+        return R48_OK;
+    const dim3 grid((unsigned)blocks);
+    const uint32_t k0 = (uint32_t)env_seed, k1 = (uint32_t)(env_seed >> 32);
+    return run("k_nt_play", n, lay.L, [&](auto len) {
+        if (depth == 1)
+            launch(k_nt_play1<len(), kPlayLanes>, grid, kBlock, stream, boards, n, lay, tables, n_steps, k0, k1, gid0,
+                   env_step, length, gain, done);
+        else
+            launch(k_nt_play2<len()>, grid, kBlock, stream, boards, n, lay, tables, n_steps, k0, k1, gid0, env_step, length,
+                   gain, done);
     });
 }
 

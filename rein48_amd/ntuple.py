@@ -35,6 +35,11 @@ LAYOUTS = {
 }
 
 
+# steps per launch of NTupleNet.play_episodes, by depth: a launch at 2^16 boards stays under 100 ms
+# on an MI355X (DESIGN.md section 16 has the measured launch times)
+PLAY_CHUNK = {1: 1000, 2: 100}
+
+
 def layout_cells(layout):
     """A layout name or a sequence of equal-length cell tuples -> tuple of tuples of ints."""
     cells = LAYOUTS[layout] if isinstance(layout, str) else layout
@@ -208,6 +213,71 @@ class NTupleNet:
             def policy(boards, t):
                 return self.search3(boards.contiguous())[0]
         return policy
+
+    def play(self, env, n_steps, depth=1, length=None, gain=None, done=None):
+        """n_steps x (policy(depth), env.step) on env's boards in ONE launch, every board in registers
+        throughout -> (boards, length int32 [n], gain int32 [n], done uint8 [n]). The boards, done
+        and env.counters end exactly where n_steps calls of env.step(self.policy(depth)(...)) leave
+        them (no auto-reset), bit for bit, so a following env.step draws the same spawns. length +=
+        the steps that changed a board, gain += their merge rewards: pass the tensors of an earlier
+        call and chunked calls add up (allocated zero where None). A board without a legal move is
+        finished and costs nothing more; a wave stops once all its boards are. depth 1 or 2."""
+        if depth not in (1, 2):
+            raise ValueError("play depth is 1 or 2, got %r (three plies: play_episodes)" % (depth,))
+        boards = env.boards
+        if boards.device != self.device:
+            raise ValueError("the env is on %s, the net on %s" % (boards.device, self.device))
+        n = _boards(boards)
+        n_steps = int(n_steps)
+        length = torch.zeros(n, dtype=torch.int32, device=self.device) if length is None else length
+        gain = torch.zeros(n, dtype=torch.int32, device=self.device) if gain is None else gain
+        length, gain = _out(length, "length", torch.int32, (n,), boards), _out(gain, "gain", torch.int32, (n,), boards)
+        done = torch.zeros(n, dtype=torch.uint8, device=self.device) if done is None else done
+        done = _out(done, "done", torch.uint8, (n,), boards)      # n_steps == 0 leaves it as it is
+        step, reset = env.counters
+        check(self._lib.r48_ntuple_play(ptr(boards), n, *self._lay(), ptr(self.tables), depth, n_steps, env.seed,
+                                        env.board_offset, step, ptr(length), ptr(gain), ptr(done), _stream(boards)))
+        env.counters = ((step + n_steps) & 0xFFFFFFFF, reset)
+        return boards, length, gain, done
+
+    @torch.no_grad()
+    def play_episodes(self, n_boards, seed=0, depth=1, max_steps=20_000, chunk=None, return_scores=False):
+        """evaluate.play_episodes(self.policy(depth), n_boards, seed=seed, ...) through play: the
+        same dict, every value equal to the last bit except steps_run, which is a multiple of chunk,
+        plus mean_gain (the mean sum of merge rewards). The boards are played in launches of `chunk`
+        steps (default PLAY_CHUNK[depth]) with one host check of done in between. depth 3 has no
+        fused kernel and goes to evaluate.play_episodes."""
+        if depth not in (1, 2, 3):
+            raise ValueError("play_episodes depth is 1, 2 or 3, got %r" % (depth,))
+        if depth == 3:
+            from .evaluate import play_episodes
+            return play_episodes(self.policy(3), n_boards, device=self.device, seed=seed, max_steps=max_steps,
+                                 return_scores=return_scores)
+        chunk = PLAY_CHUNK[depth] if chunk is None else int(chunk)
+        if chunk <= 0:
+            raise ValueError("chunk must be positive, got %r" % (chunk,))
+        env = VecGame(n_boards, device=self.device, seed=seed)
+        env.reset()
+        length = torch.zeros(n_boards, dtype=torch.int32, device=self.device)
+        gain = torch.zeros(n_boards, dtype=torch.int32, device=self.device)
+        done = torch.zeros(n_boards, dtype=torch.uint8, device=self.device)
+        t = 0
+        while t < max_steps:
+            k = min(chunk, max_steps - t)
+            self.play(env, k, depth, length, gain, done)
+            t += k
+            if bool((done != 0).all()):
+                break
+        score = env.score().double()
+        top = env.boards.max(dim=1).values.long()
+        hist = torch.bincount(top, minlength=18).double() / n_boards
+        out = {"boards": n_boards, "mean_score": float(score.mean()), "max_score": float(score.max()),
+               "mean_length": float(length.double().mean()), "finished": float((done != 0).double().mean()),
+               "steps_run": t, "max_tile_exponent_hist": {int(e): float(f) for e, f in enumerate(hist) if f > 0},
+               "mean_gain": float(gain.double().mean())}
+        if return_scores:
+            out["scores"] = score.cpu()
+        return out
 
     def state_dict(self):
         st = {"cells": [list(t) for t in self.cells], "tables": self.tables.detach().to("cpu", copy=True)}

@@ -5,6 +5,7 @@
     python tools/exp_ntuple.py --tc [--out DIR] [--sizes 65536,1048576] [--scores]
     python tools/exp_ntuple.py --search3 [--out DIR] [--sizes 256,4096,16384] [--scores] [--episodes N] [--ab-lib SO]
     python tools/exp_ntuple.py --fused [--out DIR] [--sizes 1024,4096,65536,1048576] [--scores] [--episodes N]
+    python tools/exp_ntuple.py --play [--out DIR] [--sizes 4096,65536] [--episodes N] [--ab-lib SO]
 
 For both named layouts and each board count: device-event times (5 warm-up calls, median of 7
 windows of 20 calls) of value, act, accumulate and apply with their table loads or atomics per
@@ -56,6 +57,18 @@ a synchronise), with the windows' min-max spread next to the difference. Then de
 td_act against act + accumulate, act and accumulate on the same inputs. With --scores: the 4x6 TC
 recipe (4,096 boards, alpha 1.0, seed 0) for 10,000 unfused steps, the fused steps that fit in the
 same wall time, and the depth-1 score of each (--episodes, eval seed 13). Writes exp_ntuple_fused.json.
+
+--play: whole games in one launch (NTupleNet.play / play_episodes, r48_ntuple_play). On the tables of
+the recorded recipes (lines-squares 1,024 x 2,000 TD(0), 4x6 4,096 x 10,000 TC) and at depths 1 and 2:
+--episodes (default 4,096, eval seed 13) whole episodes through play_episodes and through
+evaluate.play_episodes(net.policy(depth)) in the same process, each run twice and the second timed
+(wall seconds ending in a synchronise, device milliseconds between events around the call), scores
+compared bit for bit; the device time per step on 4,096 and 2^16 live boards of play against act (or
+search) + env.step in alternated windows; and the device time of single launches of 250 .. 2,000
+(depth 1) and 25 .. 200 (depth 2) steps at 2^16 boards, the figures behind ntuple.PLAY_CHUNK.
+--ab-lib SO: another build of the library (-DR48_NT_PLAY_LANES=4: four lanes per board at depth 1)
+whose r48_ntuple_play is alternated with this one's, boards compared bit for bit. Writes
+exp_ntuple_play.json.
 """
 import argparse
 import json
@@ -685,6 +698,175 @@ def main_fused(args):
         save()
 
 
+def timed(fn):
+    """(result, wall seconds ending in a synchronise, device milliseconds between two events around the call)."""
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0, e0.elapsed_time(e1)
+
+
+def play_of_library(path, net):
+    """NTupleNet.play through r48_ntuple_play of another build of the library (-DR48_NT_PLAY_LANES=4)."""
+    import ctypes as C
+    from rein48_amd import _lib
+    f = C.CDLL(path).r48_ntuple_play
+    f.restype, f.argtypes = _lib.SIGNATURES["r48_ntuple_play"]
+
+    def play(env, n_steps, depth, length, gain, done):
+        step, reset = env.counters
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(f(_lib.ptr(env.boards), env.n, *net._lay(), _lib.ptr(net.tables), depth, n_steps, env.seed,
+                     env.board_offset, step, _lib.ptr(length), _lib.ptr(gain), _lib.ptr(done), stream))
+        env.counters = ((step + n_steps) & 0xFFFFFFFF, reset)
+    return play
+
+
+def play_step_times(net, n, depth, k=20, ab_lib=None):
+    """Device time per step on n live boards (running games): play's k steps in one launch against k x
+    (act or search, env.step), alternated windows; both start every call from the same boards and
+    step counter (one 16n-byte copy each, inside the window). With ab_lib, the other build's play too,
+    its boards compared bit for bit."""
+    start = running_boards(n)
+    env = VecGame(n, device=DEV, seed=7)
+    length, gain = (torch.zeros(n, dtype=torch.int32, device=DEV) for _ in range(2))
+    done = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    policy = net.policy(depth)
+
+    def begin():
+        env.boards.copy_(start)
+        env.counters = (150, 0)
+
+    def fused():
+        begin()
+        net.play(env, k, depth, length, gain, done)
+
+    def composed():
+        begin()
+        for t in range(k):
+            env.step(policy(env.boards, t))
+    fns = {"play": fused, "composed": composed}
+    res = {"boards": n, "depth": depth, "steps_per_call": k}
+    composed()
+    want = env.boards.clone()
+    fused()
+    res["play_equals_composed"] = bool(torch.equal(env.boards, want))
+    res["alive_after_the_call"] = float((done == 0).float().mean())
+    if ab_lib:
+        other = play_of_library(ab_lib, net)
+
+        def fused_other():
+            begin()
+            other(env, k, depth, length, gain, done)
+        fused_other()
+        res["other_build_equals_composed"] = bool(torch.equal(env.boards, want))
+        fns["play_other_build"] = fused_other
+    for name, t in alternated_ms(fns, warmup=3, windows=7, calls=5).items():
+        res[name] = {"us_per_step": t[0] / k * 1e3, "us_min": t[1] / k * 1e3, "us_max": t[2] / k * 1e3}
+    res["composed_over_play"] = res["composed"]["us_per_step"] / res["play"]["us_per_step"]
+    return res
+
+
+def play_launch_times(net, n, depth, chunks, ab_lib=None):
+    """The device time of single play launches of `chunk` steps at n boards, games from reset: the
+    first launch (every board alive throughout, the most children at depth 2) and the longest of the
+    first four."""
+    rows = []
+    plays = {"play": lambda env, k, le, ga, do: net.play(env, k, depth, le, ga, do)}
+    if ab_lib:
+        other = play_of_library(ab_lib, net)
+        plays["play_other_build"] = lambda env, k, le, ga, do: other(env, k, depth, le, ga, do)
+    for chunk in chunks:
+        row = {"boards": n, "depth": depth, "chunk": chunk}
+        for name, play in plays.items():
+            env = VecGame(n, device=DEV, seed=13)
+            env.reset()
+            length, gain = (torch.zeros(n, dtype=torch.int32, device=DEV) for _ in range(2))
+            done = torch.zeros(n, dtype=torch.uint8, device=DEV)
+            ms = [timed(lambda: play(env, chunk, length, gain, done))[2] for _ in range(4)]
+            row[name] = {"first_launch_ms": ms[0], "longest_of_four_ms": max(ms), "launches_ms": ms,
+                         "alive_after_four": float((done == 0).float().mean())}
+        rows.append(row)
+    return rows
+
+
+def play_episode_times(net, depth, episodes, eval_seed, ab_lib=None):
+    """Whole episodes to the end: NTupleNet.play_episodes against evaluate.play_episodes on the same
+    net in the same process, each run twice (the first run of each loads code objects), wall seconds
+    ending in a synchronise and device milliseconds between events around the call."""
+    row = {"depth": depth, "episodes": episodes, "eval_seed": eval_seed}
+    runs = {"play_episodes": lambda: net.play_episodes(episodes, seed=eval_seed, depth=depth, return_scores=True),
+            "evaluate": lambda: play_episodes(net.policy(depth), episodes, device=DEV, seed=eval_seed, return_scores=True)}
+    scores = {}
+    for name, fn in runs.items():
+        fn()
+        ev, wall, dev_ms = timed(fn)
+        scores[name] = ev.pop("scores")
+        ev.update(wall_seconds=wall, device_ms=dev_ms)
+        row[name] = ev
+    row["scores_bit_equal"] = bool(torch.equal(scores["play_episodes"], scores["evaluate"]))
+    row["wall_evaluate_over_play"] = row["evaluate"]["wall_seconds"] / row["play_episodes"]["wall_seconds"]
+    if ab_lib:                                                # the other build's mapping, the same chunks
+        from rein48_amd.ntuple import PLAY_CHUNK
+        other = play_of_library(ab_lib, net)
+
+        def to_the_end():
+            env = VecGame(episodes, device=DEV, seed=eval_seed)
+            env.reset()
+            length, gain = (torch.zeros(episodes, dtype=torch.int32, device=DEV) for _ in range(2))
+            done = torch.zeros(episodes, dtype=torch.uint8, device=DEV)
+            for _ in range(0, 20000, PLAY_CHUNK[depth]):
+                other(env, PLAY_CHUNK[depth], depth, length, gain, done)
+                if bool((done != 0).all()):
+                    break
+            return env.score().double().cpu()
+        to_the_end()
+        sc, wall, dev_ms = timed(to_the_end)
+        row["play_other_build"] = {"wall_seconds": wall, "device_ms": dev_ms,
+                                   "scores_bit_equal": bool(torch.equal(sc, scores["evaluate"]))}
+    return row
+
+
+def main_play(args):
+    """--play [--ab-lib SO]: whole games in one launch (r48_ntuple_play) against the Python loop of
+    evaluate.play_episodes, on the tables of the recorded recipes."""
+    out = {"device": torch.cuda.get_device_name(0), "ab_lib": args.ab_lib, "recipes": []}
+
+    def save():
+        if args.out:
+            os.makedirs(args.out, exist_ok=True)
+            with open(os.path.join(args.out, "exp_ntuple_play.json"), "w") as f:
+                json.dump(out, f, indent=1)
+    for layout, n_boards, steps, alpha, tc in (("lines-squares", 1024, 2000, 0.25, False), ("4x6", 4096, 10000, 1.0, True)):
+        tr = NTupleTrainer(NTupleConfig(n_boards=n_boards, layout=layout, alpha=alpha, seed=0, tc=tc), device=DEV)
+        tr.train_steps(steps)
+        torch.cuda.synchronize()
+        rec = {"layout": layout, "train_boards": n_boards, "train_steps": steps, "alpha": alpha, "tc": tc,
+               "episodes": [], "per_step": [], "launches": []}
+        out["recipes"].append(rec)
+        for depth in (1, 2):
+            r = play_episode_times(tr.net, depth, args.episodes, 13, args.ab_lib if depth == 1 else None)
+            rec["episodes"].append(r)
+            print(json.dumps(dict(r, layout=layout)), flush=True)
+            save()
+        for depth in (1, 2):
+            for n in (int(s) for s in (args.sizes or "4096,65536").split(",")):
+                r = play_step_times(tr.net, n, depth, ab_lib=args.ab_lib if depth == 1 else None)
+                rec["per_step"].append(r)
+                print(json.dumps(dict(r, layout=layout)), flush=True)
+            for r in play_launch_times(tr.net, 65536, depth, (250, 500, 1000, 2000) if depth == 1 else (25, 50, 100, 200),
+                                       args.ab_lib if depth == 1 else None):
+                rec["launches"].append(r)
+                print(json.dumps(dict(r, layout=layout)), flush=True)
+            save()
+        del tr
+        torch.cuda.empty_cache()
+
+
 def main_search(args):
     out = {"device": torch.cuda.get_device_name(0), "kernels": [], "scores": []}
     for layout in ("lines-squares", "4x6"):
@@ -714,11 +896,14 @@ def main():
     ap.add_argument("--tc", action="store_true")
     ap.add_argument("--search3", action="store_true")
     ap.add_argument("--fused", action="store_true")
+    ap.add_argument("--play", action="store_true")
     ap.add_argument("--episodes", type=int, default=4096)
     ap.add_argument("--ab-lib", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("exp_ntuple.py needs a GPU")
+    if args.play:
+        return main_play(args)
     if args.fused:
         return main_fused(args)
     if args.search3:
