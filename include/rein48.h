@@ -204,7 +204,8 @@ int r48_sample_actions(const float *logits, int64_t n, uint64_t seed, int64_t gi
  * rewards/out float[T][n], lengths int32[n] (segment length, 1..T), bootstrap float[n].
  * drop_last != 0: out[len-1] = bootstrap, out[t] = r_t + gamma*out[t+1] (the reference, whose
  * last reward never enters); drop_last == 0: the textbook n-step return. out[t] = 0 for
- * t >= len. */
+ * t >= len. Lengths are clamped to 0..T: a length below 0 counts as 0 (the whole column is 0), one
+ * above T as T. */
 int r48_discounted_returns(const float *rewards, const int32_t *lengths, const float *bootstrap,
                            int32_t T, int64_t n, float gamma, int32_t drop_last, float *out,
                            void *stream);
@@ -382,13 +383,15 @@ int r48_egreedy_actions(const float *q, int64_t n, float eps, uint64_t seed, int
 /* TD target y[i] = R + gamma * (1 - done[i]) * q_next_target[i][a*], a* = argmax of
  * q_next_online[i] (double DQN) or of q_next_target[i] when q_next_online is NULL; R = reward[i],
  * or log2(1 + reward[i]) (fp32, as torch.log2(1.0 + r)) when log2_reward != 0 -- the trainer's
- * reward transform folded in. done nullable (= 0). Q arrays float[n][4], 16-byte aligned. */
+ * reward transform folded in. done nullable (= 0); any nonzero byte is done, so (1 - done[i]) is 0
+ * for it and y[i] = R. Q arrays float[n][4], 16-byte aligned. */
 int r48_td_target(const float *reward, const uint8_t *done, const float *q_next_target,
                   const float *q_next_online, int64_t n, float gamma, int32_t log2_reward, float *y, void *stream);
 
 /* Huber loss (smooth L1, beta 1) of the update: d = q[i][action[i]] - y[i]; out[0] = mean loss,
  * out[1] = mean q[i][action[i]]; dq[i][a] = clamp(d, -1, 1) / n for a = action[i], else 0 (the
- * gradient of the mean loss). q, dq float[n][4] 16-byte aligned; workspace float[512].
+ * gradient of the mean loss). q, dq float[n][4] 16-byte aligned; workspace float[512]. Only the two
+ * low bits of an action byte count: a byte outside 0..3 selects action[i] & 3. n >= 1.
  * Deterministic (fixed-order sums). Replaces trainer.py's gather + F.smooth_l1_loss + backward. */
 int r48_huber_grad(const float *q, const int8_t *action, const float *y, int64_t n, float *dq, float *out,
                    float *workspace, void *stream);

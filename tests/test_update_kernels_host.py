@@ -1,0 +1,131 @@
+"""The float64 references of tests/update_refs.py against independent statements of the same maths, on
+the CPU: a wrong reference must not be able to agree with a wrong kernel in test_update_kernels_gpu.py.
+
+Huber against torch's smooth_l1_loss and autograd, Adam against torch.optim.Adam, the returns slab
+against the reference's own executed outputs (tests/golden/a3c_golden.json), the vectorised Philox
+against the C oracle's. RMSProp and the TD target are oracle/a3c_ref.py's and oracle/dqn_ref.py's,
+which test_a3c.py and test_dqn.py cover.
+"""
+import json
+import os
+
+import numpy as np
+import torch
+
+import update_refs as U
+from oracle import native as O
+
+
+def test_huber_reference_matches_smooth_l1_and_autograd():
+    """Loss per row and the gradient of the mean, float64 against float64 (1e-15: the same few
+    operations). The planted rows sit on and next to the |d| = 1 switch."""
+    rng = np.random.default_rng(0)
+    one = np.float32(1)
+    planted = [0.0, 1.0, -1.0, float(np.nextafter(one, np.float32(0))), -float(np.nextafter(one, np.float32(0))),
+               float(np.nextafter(one, np.float32(2))), -float(np.nextafter(one, np.float32(2))), 1e6, -1e6, 1e-20,
+               -1e-20]
+    y = rng.normal(scale=2.0, size=1003)
+    qa = rng.normal(scale=2.0, size=1003)
+    qa[:len(planted)] = y[:len(planted)] + planted
+    loss, grad = U.huber(qa, y)
+    tq = torch.tensor(qa, dtype=torch.float64, requires_grad=True)
+    rows = torch.nn.functional.smooth_l1_loss(tq, torch.tensor(y, dtype=torch.float64), reduction="none")
+    rows.mean().backward()
+    np.testing.assert_allclose(loss, rows.detach().numpy(), rtol=1e-15, atol=0)
+    np.testing.assert_allclose(grad, tq.grad.numpy(), rtol=1e-15, atol=0)
+    d = qa - y
+    assert (grad[np.abs(d) >= 1] == np.sign(d[np.abs(d) >= 1]) / d.size).all()
+
+
+def test_adam_reference_matches_torch_adam_over_6_steps():
+    """6 chained steps in float64 with zero, tiny and huge gradients: the operation order differs
+    (torch divides the step size, not the moment), so 1e-13 relative."""
+    rng = np.random.default_rng(1)
+    n = 257
+    p = rng.normal(size=n)
+    tp = torch.tensor(p, dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.Adam([tp], lr=1e-3, betas=(0.9, 0.999), eps=1e-8)
+    m, v = np.zeros(n), np.zeros(n)
+    for t in range(1, 7):
+        g = rng.normal(size=n)
+        g[::5] = 0.0
+        g[1::7] = 1e-12
+        g[2::11] = -1e4
+        tp.grad = torch.tensor(g, dtype=torch.float64)
+        opt.step()
+        p, m, v = U.adam(p, g, m, v, t)
+        np.testing.assert_allclose(p, tp.detach().numpy(), rtol=1e-13, atol=1e-15)
+    st = opt.state[tp]
+    np.testing.assert_allclose(m, st["exp_avg"].numpy(), rtol=1e-13, atol=0)
+    np.testing.assert_allclose(v, st["exp_avg_sq"].numpy(), rtol=1e-13, atol=0)
+
+
+def test_adam_reference_leaves_an_all_zero_entry_alone():
+    p, m, v = U.adam(np.array([1.5, -2.0]), np.zeros(2), np.zeros(2), np.zeros(2), 3)
+    assert (p == [1.5, -2.0]).all() and (m == 0).all() and (v == 0).all()
+
+
+def test_returns_reference_matches_every_golden_case():
+    """All 48 executed reference cases in one slab, ragged lengths: rows below the length equal the
+    golden targets (1e-12), rows from the length on are zero."""
+    g = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "a3c_golden.json")))["returns"]
+    T, n = max(len(c["rewards"]) for c in g) + 2, len(g)
+    rewards = np.full((T, n), 7.0)                          # rows past a length must not enter
+    for i, c in enumerate(g):
+        rewards[:len(c["rewards"]), i] = c["rewards"]
+    lengths = [len(c["rewards"]) for c in g]
+    boot = [c["last_target_value"] for c in g]
+    out = U.returns(rewards, lengths, boot, 0.9, True)
+    for i, c in enumerate(g):
+        np.testing.assert_allclose(out[:lengths[i], i], c["targets"], rtol=1e-12, atol=1e-12)
+        assert (out[lengths[i]:, i] == 0).all()
+
+
+def test_returns_reference_clamps_lengths_and_knows_both_modes():
+    """Hand-computed columns (gamma 0.5, bootstrap 0.5, rewards (i + 1) 10^t: every value exact)."""
+    r = np.outer([1.0, 10.0, 100.0], [1.0, 2.0, 3.0, 4.0, 5.0])                              # [T = 3][n = 5]
+    out = U.returns(r, [-2, 0, 2, 3, 6], [0.5] * 5, 0.5, True)
+    assert (out[:, :2] == 0).all()
+    np.testing.assert_array_equal(out[:, 2], [3.25, 0.5, 0.0])
+    np.testing.assert_array_equal(out[:, 3], [24.125, 40.25, 0.5])
+    np.testing.assert_array_equal(out[:, 4], [30.125, 50.25, 0.5])                           # length 6 counts as 3
+    tb = U.returns(r, [-2, 0, 2, 3, 6], [0.5] * 5, 0.5, False)
+    assert (tb[:, :2] == 0).all()
+    np.testing.assert_array_equal(tb[:, 2], [18.125, 30.25, 0.0])
+    np.testing.assert_array_equal(tb[:, 4], [155.0625, 300.125, 500.25])
+
+
+def test_vectorised_philox_matches_the_oracle():
+    """A few hundred counters, board ids above 2^32 and the all-ones counter among them, two keys."""
+    rng = np.random.default_rng(2)
+    n = 300
+    ctr = rng.integers(0, 2 ** 32, size=(n, 4), dtype=np.uint64)
+    gid = (2 ** 32 + 5) + np.arange(40, dtype=np.uint64)
+    ctr[:40, 0], ctr[:40, 1] = gid & np.uint64(0xFFFFFFFF), gid >> np.uint64(32)
+    ctr[40] = 0xFFFFFFFF
+    ctr[41] = 0
+    for key in ((77, 0), (0xDEADBEEF, 0xFFFFFFFF)):
+        got = U.philox4x32_10(ctr, key)
+        want = np.stack([O.philox([int(x) for x in row], list(key)) for row in ctr])
+        np.testing.assert_array_equal(got, want)
+
+
+def test_sample_uniforms_follow_the_draw_contract():
+    seed, gid0, ctr, n = (5 << 32) | 77, 2 ** 32 - 3, 0xFFFFFFFF, 9
+    u = U.sample_uniforms(n, seed, gid0, ctr)
+    for i in range(n):
+        g = gid0 + i
+        w = O.philox([g & 0xFFFFFFFF, g >> 32, ctr, 0xA3C], [seed & 0xFFFFFFFF, seed >> 32])
+        assert u[i] == (int(w[0]) >> 8) / 16777216.0 and 0.0 <= u[i] < 1.0
+
+
+def test_bf16_half_ulp_bounds_round_to_nearest():
+    """bf16 keeps 8 significant bits: rounding 1 + 2^-8 (a tie, to even: 1) errs by 2^-8, more than
+    2^-9 |x|; half an ulp of the value's own binade is the bound that holds everywhere."""
+    x = torch.tensor([1.0 + 2.0 ** -8, 1.99, 3.0e-5, 255.5, 1.0e6], dtype=torch.float64)
+    x = torch.cat([x, torch.linspace(0.5, 4.0, 9973, dtype=torch.float64)])
+    err = (x.float().to(torch.bfloat16).double() - x).abs().numpy()
+    hu = U.bf16_half_ulp(x.numpy())
+    assert (err <= hu).all() and err[0] == 2.0 ** -8 and err[0] > 2.0 ** -9 * float(x[0])
+    assert (hu >= 2.0 ** -9 * x.numpy() * (1 - 1e-15)).all() and (hu <= 2.0 ** -8 * x.numpy()).all()
+    assert U.bf16_half_ulp(0.0) == 0.0

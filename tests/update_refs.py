@@ -1,0 +1,88 @@
+"""float64 numpy references for the kernels at the two ends of the DQN and A3C updates -- a helper of
+test_update_kernels_host.py (which checks these references on the CPU) and test_update_kernels_gpu.py
+(which holds the kernels to them). Not collected by pytest.
+
+  philox4x32_10   vectorised Philox4x32-10 (oracle.native.philox one counter at a time)
+  sample_uniforms r48_sample_actions' 24-bit uniform of every row
+  huber           per-row smooth-L1 loss (beta 1) and the gradient of its mean
+  adam            one torch.optim.Adam step (bias-corrected, eps outside the square root)
+  returns         r48_discounted_returns' [T][n] slab, lengths clamped to 0..T
+  q_head          the Q head Linear(1024 -> 4) and its backward, with the magnitude sums of the bounds
+RMSProp and the TD target are oracle/a3c_ref.py's and oracle/dqn_ref.py's.
+"""
+import numpy as np
+
+from oracle import a3c_ref as R
+
+U = 2.0 ** -24          # fp32 unit roundoff (round to nearest)
+MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(ctr, key):
+    """ctr uint32-valued [n, 4], key (k0, k1) -> uint32 [n, 4]: ten rounds of Philox4x32."""
+    c = [np.asarray(ctr)[:, k].astype(np.uint64) & MASK32 for k in range(4)]
+    k0, k1 = np.uint64(int(key[0]) & 0xFFFFFFFF), np.uint64(int(key[1]) & 0xFFFFFFFF)
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    s = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]                       # 32 x 32 -> 64 bits: no overflow in uint64
+        c = [(p1 >> s) ^ c[1] ^ k0, p1 & MASK32, (p0 >> s) ^ c[3] ^ k1, p0 & MASK32]
+        k0 = (k0 + np.uint64(0x9E3779B9)) & MASK32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & MASK32
+    return np.stack(c, 1).astype(np.uint32)
+
+
+def sample_uniforms(n, seed, gid0, ctr):
+    """u[i] of r48_sample_actions: Philox4x32-10(key = seed, counter = {gid lo, gid hi, ctr, 0xA3C}),
+    gid = gid0 + i, u = (w0 >> 8) / 2^24. float64 (exact: 24 bits)."""
+    gid = np.arange(n, dtype=np.uint64) + np.uint64(gid0)
+    c = np.stack([gid & MASK32, gid >> np.uint64(32), np.full(n, ctr & 0xFFFFFFFF, np.uint64),
+                  np.full(n, 0xA3C, np.uint64)], 1)
+    w = philox4x32_10(c, (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+    return (w[:, 0] >> np.uint32(8)).astype(np.float64) / 16777216.0
+
+
+def huber(qa, y):
+    """qa, y [n] -> (loss per row [n], gradient of the MEAN loss w.r.t. qa [n]), float64."""
+    d = np.asarray(qa, np.float64) - np.asarray(y, np.float64)
+    ad = np.abs(d)
+    return np.where(ad < 1.0, 0.5 * d * d, ad - 0.5), np.clip(d, -1.0, 1.0) / d.size
+
+
+def adam(p, g, m, v, t, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):
+    """One step with the 1-based step count t -> (p, m, v); float64 in, float64 out."""
+    m = b1 * m + (1.0 - b1) * g
+    v = b2 * v + (1.0 - b2) * g * g
+    c1, c2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+    return p - (lr / c1) * m / (np.sqrt(v / c2) + eps), m, v
+
+
+def returns(rewards, lengths, bootstrap, gamma, drop_last):
+    """[T][n] targets: column i is R.target_values over its first clamp(lengths[i], 0, T) rewards,
+    0 from there on (a column of length 0 is all zero)."""
+    rewards = np.asarray(rewards, np.float64)
+    T, n = rewards.shape
+    out = np.zeros((T, n))
+    for i in range(n):
+        L = int(min(max(int(lengths[i]), 0), T))
+        if L:
+            out[:L, i] = R.target_values(rewards[:L, i], float(bootstrap[i]), gamma, drop_last=drop_last)
+    return out
+
+
+def q_head(h, w, b, dq):
+    """h [B, 1024], w [4, 1024], b [4], dq [B, 4], all float64 holding the values the kernels use
+    (bf16-valued h, w, b and dq). -> dict of q, dh, dw, db and the sums of magnitudes |.| that the
+    fp32 summation bounds are stated over."""
+    return {"q": h @ w.T + b, "q_mag": np.abs(h) @ np.abs(w).T,
+            "dh": dq @ w, "dh_mag": np.abs(dq) @ np.abs(w),
+            "dw": dq.T @ h, "dw_mag": np.abs(dq).T @ np.abs(h),
+            "db": dq.sum(0), "db_mag": np.abs(dq).sum(0)}
+
+
+def bf16_half_ulp(x):
+    """Half a bf16 ulp (8 significant bits) in the binade of |x|: 2^(floor(log2 |x|) - 8); the error of
+    rounding x to the nearest bf16 is at most this. Between 2^-9 |x| and 2^-8 |x|; 0 at 0."""
+    x = np.abs(np.asarray(x, np.float64))
+    _, e = np.frexp(x)                                        # x = f 2^e, f in [0.5, 1)
+    return np.where(x > 0, np.ldexp(1.0, e - 1 - 8), 0.0)
