@@ -660,6 +660,22 @@ int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int
 int r48_ntuple_search3(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
                        const float *tables, int8_t *actions, float *q, uint8_t *legal, void *stream);
 
+/* The search at a depth chosen per board, 1..4 plies, one kernel, one board per workgroup. rule is
+ * uint8[17] ON THE HOST, every entry in 1..4: board i is searched at depth d_i = rule[the number
+ * of zero cells of board i]. actions, q and legal are those of r48_ntuple_search(depth = d_i) for
+ * d_i = 1 or 2 and of r48_ntuple_search3 for d_i = 3, bit for bit; d_i = 4 writes Q_4 of the
+ * recursion above (a depth-3 search of each of the board's children, then the averaging step),
+ * the same arithmetic and tree order one level up. depth_out uint8[n] (nullable) = d_i, also for
+ * a board without a legal move (whose q is -inf and action 0 as at every depth). q is bitwise
+ * reproducible and does not depend on the board's place in the batch, on n or on the rule's
+ * other entries. Cost: a depth-4 search of a board with many blanks takes about a hundred times
+ * its depth-3 search -- the rule is the cost guard; keep 4 to boards with few blanks. Stateless.
+ * R48_EINVAL (before any HIP call) as r48_ntuple_search3, and for a NULL rule, a rule entry
+ * outside 1..4, or n beyond 2^31 - 1 boards (the grid). n == 0 is a no-op after these checks. */
+int r48_ntuple_search_ruled(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                            const float *tables, const uint8_t *rule, int8_t *actions, float *q,
+                            uint8_t *legal, uint8_t *depth_out, void *stream);
+
 /* Whole games in one launch: search and env step for n_steps steps, every board in registers from
  * its load to its store. For t = 0 .. n_steps - 1, board i
  *   1. takes the action r48_ntuple_act returns for it (depth 1) or r48_ntuple_search(depth = 2)

@@ -17,8 +17,8 @@
 // Summation order (the contract every kernel here shares, so value and act agree bit for bit):
 // fp32, starting from 0, hits in the order p = 8t + g = 0, 1, ..., 8m - 1.
 //
-// The search (k_nt_search, k_nt_search3, and nt_search_board for one board on the host). For a move a that
-// changes the board: afterstate s_a, merge reward r_a, and
+// The search (k_nt_search, k_nt_search3, k_nt_search_ruled, and nt_search_board for one board on
+// the host). For a move a that changes the board: afterstate s_a, merge reward r_a, and
 //     depth 1   Q(a) = (float)r_a + V(s_a)                                  (act's score)
 //     depth 2   Q(a) = (float)r_a + S_a / (float)(10 |E|),  E = the empty cells of s_a,
 //               S_a = sum over c in E of (9 leaf(s_a[c <- 1]) + leaf(s_a[c <- 2])),
@@ -37,15 +37,30 @@
 //     commutes, so every lane of the butterfly holds these bits. The order depends on nothing
 //     but the cell numbers: not on the batch, on n, or on which cells are empty.
 //
-// The same, recursively, for any number of plies k (k_nt_search3 runs k = 3, nt_search_board 1..3):
+// The same, recursively, for any number of plies k (k_nt_search3 runs k = 3, k_nt_search_ruled and
+// nt_search_board 1..4):
 //     best_k(board) = max over the board's legal moves a of Q_k(a), 0 where it has none
 //     Q_1(a)        = (float)r_a + V(s_a)
 //     Q_k(a), k > 1 = (float)r_a + S_a / (float)(10 |E|),  S_a = nt_sum16 of the sixteen cell terms
 //                     x_c = fmaf(9, best_(k-1)(s_a[c <- 1]), best_(k-1)(s_a[c <- 2])), x_c = +0 where
 //                     cell c of s_a holds a tile
-// Depth 2 is the above with leaf = best_1; depth 3's leaf is best_2. The arithmetic is the same at
-// every level: fp32, nt_fma for a cell term, the butterfly's order, one division by 10 |E| per
-// level (nt_q2). The max over the legal moves of fp32 scores does not depend on their order.
+// Depth 2 is the above with leaf = best_1; depth 3's leaf is best_2, depth 4's best_3:
+//     Q_4(a) = (float)r_a + nt_sum16(x) / (float)(10 |E|),
+//     x_c = nt_fma(9, best_3(s_a[c <- 1]), best_3(s_a[c <- 2])).
+// The arithmetic is the same at every level: fp32, nt_fma for a cell term, the butterfly's order,
+// one division by 10 |E| per level (nt_q2). The max over the legal moves of fp32 scores does not
+// depend on their order.
+//
+// The ruled search (k_nt_search_ruled, nt_search_board_ruled) chooses the depth per board. A RULE
+// is uint8 depth_of_blanks[17], every entry in 1..4; board i is searched at depth
+//     d_i = rule[blanks(board_i)],  blanks = the zero cells of the root board, 0..16,
+// and its actions / q / legal are exactly those of the search at depth d_i above: the bits of
+// k_nt_search at d_i = 1 or 2 and of k_nt_search3 at d_i = 3. depth_out[i] (nullable) = d_i for
+// every board, one without a legal move included (its q is -inf, its action 0, and depth_out is
+// still rule[blanks]). As everywhere here, q does not depend on where the board is in the batch,
+// on n, on how the children were dealt or on which wave did what -- nor on the rule's other
+// entries. A roomy board at depth 4 costs about a hundred times depth 3: the rule is the cost
+// guard.
 #pragma once
 #include <stdint.h>
 
@@ -452,8 +467,8 @@ inline float nt_q_level(const Board &s, uint32_t r, const NtLayout &lay, const f
     return nt_q2(r, nt_sum16(x), blanks(s).n);
 }
 
-// The whole search of one board, serially, at depth 1, 2 or 3: the host's restatement of
-// k_nt_search and k_nt_search3, which run the same nt_leaf / nt_fma / nt_q2 / nt_argmax4 but
+// The whole search of one board, serially, at depth 1..4: the host's restatement of k_nt_search,
+// k_nt_search3 and k_nt_search_ruled, which run the same nt_leaf / nt_fma / nt_q2 / nt_argmax4 but
 // spread the children over lanes and waves and sum with the butterfly. Returns the action; q[4]
 // and legal as the kernels write them.
 template <int L>
@@ -475,6 +490,50 @@ inline uint32_t nt_search_board(const Board &b, const NtLayout &lay, const float
         q[a] = nt_q_level<L>(s, r, lay, tables, depth);
     }
     return nt_argmax4(q[0], q[1], q[2], q[3]);
+}
+
+// ---- the ruled search: the depth by the board's blanks -----------------------------------------
+static constexpr int kNtRuleLen = 17;      // blanks 0..16
+static constexpr int kNtMaxDepth = 4;
+
+// NULL, or what is wrong with a rule
+inline const char *nt_rule_check(const uint8_t *rule)
+{
+    if (!rule)
+        return "rule is NULL";
+    for (int k = 0; k < kNtRuleLen; k++)
+        if (rule[k] < 1 || rule[k] > kNtMaxDepth)
+            return "a rule entry is not in 1..4";
+    return nullptr;
+}
+
+// A checked rule in one word, as it travels to the kernel: depth - 1 of k blanks at bits 2k, 2k + 1.
+inline uint64_t nt_rule_pack(const uint8_t *rule)
+{
+    uint64_t w = 0;
+    for (int k = 0; k < kNtRuleLen; k++)
+        w |= (uint64_t)(rule[k] - 1u) << (2 * k);
+    return w;
+}
+
+R48_HD uint32_t nt_packed_rule_depth(uint64_t packed, const Board &b)
+{
+    return 1u + ((uint32_t)(packed >> (2u * blanks(b).n)) & 3u);
+}
+
+// d_i of the contract: rule[blanks(board)]
+inline uint32_t nt_rule_depth(const uint8_t *rule, const Board &b) { return rule[blanks(b).n]; }
+
+// The ruled contract for one board: nt_search_board at rule[blanks]; depth_out (nullable) as the
+// kernel writes it, whether or not the board has a legal move.
+template <int L>
+inline uint32_t nt_search_board_ruled(const Board &b, const NtLayout &lay, const float *tables, const uint8_t *rule,
+                                      float q[4], uint32_t &legal, uint8_t *depth_out)
+{
+    const uint32_t d = nt_rule_depth(rule, b);
+    if (depth_out)
+        *depth_out = (uint8_t)d;
+    return nt_search_board<L>(b, lay, tables, (int)d, q, legal);
 }
 
 // ---- playing whole games ----------------------------------------------------------------------

@@ -8,17 +8,25 @@
 //   nt_add_hits      cnt[e] += 1, acc[e] += delta over 8m hits   k_nt_accumulate, k_nt_td_act
 //   nt_owned_hits    the exchange walk that finds an entry's     k_nt_apply (plain mean step),
 //                    one owner lane                              k_nt_apply_tc (TC rule)
-//   nt_wave_q2       the depth-2 search of a board by a wave     k_nt_search<L, 2>, k_nt_search3
-//   nt_row_q,        how a search ends: butterfly, Q, the four   nt_wave_q2, k_nt_search,
-//   nt_write_search  rows' scores, argmax, the writes            k_nt_search3
+//   nt_wave_q2       the depth-2 search of a board by a wave     k_nt_search<L, 2>, k_nt_search3,
+//                                                                k_nt_search_ruled, nt_wave_q3
+//   nt_wave_q1       the depth-1 search in the same lane mapping k_nt_search<L, 1>, k_nt_search_ruled
+//   nt_wave_q3       the depth-3 search of a board by a wave:    k_nt_search_ruled (depth 4)
+//                    nt_wave_q2 on each child, one after another
+//   nt_slot_term     a slot lane's cell term from the leaves     nt_wave_q2, nt_wave_q3
+//   nt_root_moves,   one board per workgroup: wave 0's root      k_nt_search3, k_nt_search_ruled
+//   nt_deal_and_     moves, then children dealt from an LDS
+//   finish           counter and finished by the last wave
+//   nt_row_q,        how a search ends: butterfly, Q, the four   nt_wave_q2, nt_wave_q3, k_nt_search,
+//   nt_write_search  rows' scores, argmax, the writes            nt_deal_and_finish
 //   nt_play_store    what a played board leaves behind           k_nt_play1 (over nt_act_board),
 //                                                                k_nt_play2 (over nt_wave_q2)
 // and r48_ntuple.h's nt_value (k_nt_value and everything above) and nt_tc_rate_mean (k_nt_tc_rate).
 // k_nt_td_act is act, the trainer's TD error and accumulate for the previous step's afterstates in
-// one launch: the fused training step. k_nt_search runs one board per WAVE, k_nt_search3 one per
-// WORKGROUP; every other kernel one board per lane with one 16-byte board load. All are templated
-// on the tuple length L so the cell loops unroll; the expanded layout travels by value in the
-// kernel arguments (wave-uniform).
+// one launch: the fused training step. k_nt_search runs one board per WAVE, k_nt_search3 and
+// k_nt_search_ruled one per WORKGROUP; every other kernel one board per lane with one 16-byte
+// board load. All are templated on the tuple length L so the cell loops unroll; the expanded
+// layout travels by value in the kernel arguments (wave-uniform).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -300,6 +308,8 @@ __global__ __launch_bounds__(kBlock) void k_nt_tc_rate(const int8_t *__restrict_
 // read from lanes 0, 16, 32, 48; those lanes write q, lane 0 the action and the legal set.
 constexpr int kSearchBoards = kBlock / 64;   // boards (waves) per workgroup
 
+__device__ __forceinline__ uint32_t uniform_word(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+
 // How a search at depth 2 or 3 ends in lane 16 a + c: S_a by the xor butterfly over the row's
 // cell terms x, then the header's Q(a); -inf where move a is illegal.
 __device__ __forceinline__ float nt_row_q(float x, bool ok, uint32_t reward, const r48::Board &afterstate)
@@ -325,6 +335,18 @@ __device__ __forceinline__ void nt_write_search(float qa, uint32_t lane, uint32_
         if (legal)
             legal[i] = (uint8_t)lg;
     }
+}
+
+// The header's x_c in a slot lane from the wave's leaves, +0 in every other lane: the leaf of child
+// j is in lane j & 63, in leaf0 for j < 64 and in leaf1 beyond, and the slot of rank rho (rank2 =
+// 2 rho) owns children 2 rho and 2 rho + 1. rank2 is even, so rank2 + 1 stays in the wave.
+__device__ __forceinline__ float nt_slot_term(float leaf0, float leaf1, uint32_t rank2, bool slot)
+{
+    const int src = (int)(rank2 & 63u);
+    const float two0 = __shfl(leaf0, src), four0 = __shfl(leaf0, src + 1);
+    const float two1 = __shfl(leaf1, src), four1 = __shfl(leaf1, src + 1);
+    const bool late = rank2 >= 64u;
+    return slot ? r48::nt_fma(9.0f, late ? two1 : two0, late ? four1 : four0) : 0.0f;
 }
 
 // The depth-2 search of a board that every lane of the wave holds (the lane mapping above): the
@@ -358,12 +380,92 @@ __device__ __forceinline__ float nt_wave_q2(const r48::Board &b, uint32_t lane, 
         leaf0 = base == 0u ? leaf : leaf0;
         leaf1 = base == 0u ? leaf1 : leaf;
     }
-    const int src = (int)(rank2 & 63u);
-    const float two0 = __shfl(leaf0, src), four0 = __shfl(leaf0, src + 1);
-    const float two1 = __shfl(leaf1, src), four1 = __shfl(leaf1, src + 1);
-    const bool late = rank2 >= 64u;
-    const float x = slot ? r48::nt_fma(9.0f, late ? two1 : two0, late ? four1 : four0) : 0.0f;
-    return nt_row_q(x, ok, r, s);
+    return nt_row_q(nt_slot_term(leaf0, leaf1, rank2, slot), ok, r, s);
+}
+
+// The depth-1 search in the same lane mapping: the first lane of a row scores s_a itself, the row
+// reads it. Shared by k_nt_search<L, 1> and k_nt_search_ruled.
+template <int L>
+__device__ __forceinline__ float nt_wave_q1(const r48::Board &b, uint32_t lane, const r48::NtLayout &lay,
+                                            const float *__restrict__ tables, uint32_t &lg)
+{
+    const uint32_t a = lane >> 4, c = lane & 15u;
+    const r48::Moves4 m = r48::move_rows4<true>(b);
+    lg = r48::nt_legal4(m, b);
+    const bool ok = ((lg >> a) & 1u) != 0u;
+    float x = 0.0f;
+    if (ok && c == 0u)
+        x = r48::nt_score<L>(r48::nt_pick(m, a), r48::nt_pick_reward(m, a), lay, tables);
+    return ok ? __shfl(x, (int)(lane & 48u)) : -__builtin_inff();
+}
+
+// The largest of a wave's four row scores, 0 where the board has no legal move: best_k of the
+// board the wave searched at depth k. An illegal move holds -inf, so the plain max is the max over
+// the legal ones.
+__device__ __forceinline__ float nt_wave_best(float qa, uint32_t lg)
+{
+    const float b0 = __shfl(qa, 0), b1 = __shfl(qa, 16), b2 = __shfl(qa, 32), b3 = __shfl(qa, 48);
+    return lg ? fmaxf(fmaxf(b0, b1), fmaxf(b2, b3)) : 0.0f;
+}
+
+// what nt_wave_q3 keeps of its board across the searches of the board's children, one per wave
+struct WaveRoot {
+    uint32_t after[4][4];   // the afterstate of move a, words w0 .. w3
+    uint32_t reward[4];
+};
+
+// The depth-3 search of a board that every lane of the wave holds: nt_wave_q2 with the leaf one
+// level deeper. The board's children (2 to 120, numbered as nt_wave_q2 numbers them: child j is
+// spawn 1 + (j & 1) in the slot of rank j >> 1 of the ballot M) are searched one after another by
+// the whole wave, nt_wave_q2 on each, and best_2(child j) is kept in lane j & 63 -- in its first
+// leaf register for j < 64, its second beyond, by selects -- which is where nt_wave_q2's tail
+// reads its leaves: by rank2 with __shfl, then nt_fma, then nt_row_q. The four afterstates do not
+// stay in registers across the inner searches (held there, the 3-ply kernel's first form took
+// 100 to 168 VGPRs): the first lane of each row leaves its afterstate in the wave's own LDS slot
+// `keep`, the loop reads a child's parent from there with a uniform address and the tail its
+// row's. Only this wave touches `keep`, and a wave's LDS operations complete in order.
+template <int L>
+__device__ __forceinline__ float nt_wave_q3(const r48::Board &b, uint32_t lane, const r48::NtLayout &lay,
+                                            const float *__restrict__ tables, WaveRoot &keep, uint32_t &lg)
+{
+    const uint32_t a = lane >> 4, c = lane & 15u;
+    uint64_t M;
+    {
+        const r48::Moves4 m = r48::move_rows4<true>(b);
+        lg = uniform_word(r48::nt_legal4(m, b));   // the same in every lane: a scalar across the loop
+        const r48::Board s = r48::nt_pick(m, a);
+        M = __ballot(((lg >> a) & 1u) != 0u && r48::nt_cell(s, c) == 0u);
+        if (c == 0u) {
+            keep.after[a][0] = s.w0;
+            keep.after[a][1] = s.w1;
+            keep.after[a][2] = s.w2;
+            keep.after[a][3] = s.w3;
+            keep.reward[a] = r48::nt_pick_reward(m, a);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint32_t kids = 2u * (uint32_t)__popcll(M);
+    float leaf0 = 0.0f, leaf1 = 0.0f;
+#pragma unroll 1
+    for (uint32_t j = 0u; j < kids; j++) {   // uniform
+        const uint32_t p = r48::nt_select_bit(M, j >> 1);   // < 64
+        const uint32_t *sa = keep.after[p >> 4];
+        r48::Board child{sa[0], sa[1], sa[2], sa[3]};
+        r48::place(child, p & 15u, 1u + (j & 1u), true);
+        uint32_t lg2;
+        const float q2a = nt_wave_q2<L>(child, lane, lay, tables, lg2);
+        const float best = nt_wave_best(q2a, uniform_word(lg2));
+        const bool mine = lane == (j & 63u);
+        leaf0 = (mine && j < 64u) ? best : leaf0;
+        leaf1 = (mine && j >= 64u) ? best : leaf1;
+    }
+    const bool ok = ((lg >> a) & 1u) != 0u;
+    const bool slot = ((M >> lane) & 1ull) != 0ull;
+    const uint32_t rank2 = 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
+    const r48::Board s{keep.after[a][0], keep.after[a][1], keep.after[a][2], keep.after[a][3]};
+    return nt_row_q(nt_slot_term(leaf0, leaf1, rank2, slot), ok, keep.reward[a], s);
 }
 
 template <int L, int DEPTH>
@@ -376,21 +478,14 @@ __global__ __launch_bounds__(kBlock) void k_nt_search(const int8_t *__restrict__
     const int64_t i = (int64_t)blockIdx.x * kSearchBoards + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (i >= n)
         return;   // the whole wave
-    const uint32_t lane = threadIdx.x & 63u, a = lane >> 4, c = lane & 15u;
+    const uint32_t lane = threadIdx.x & 63u;
     const r48::Board b = r48::load_board(boards, i);
     uint32_t lg;
     float qa;
-    if (DEPTH == 1) {
-        const r48::Moves4 m = r48::move_rows4<true>(b);
-        lg = r48::nt_legal4(m, b);
-        const bool ok = ((lg >> a) & 1u) != 0u;
-        float x = 0.0f;
-        if (ok && c == 0u)
-            x = r48::nt_score<L>(r48::nt_pick(m, a), r48::nt_pick_reward(m, a), lay, tables);
-        qa = ok ? __shfl(x, (int)(lane & 48u)) : -__builtin_inff();
-    } else {
+    if (DEPTH == 1)
+        qa = nt_wave_q1<L>(b, lane, lay, tables, lg);
+    else
         qa = nt_wave_q2<L>(b, lane, lay, tables, lg);
-    }
     nt_write_search(qa, lane, lg, i, actions, q, legal);
 }
 
@@ -425,8 +520,6 @@ constexpr int kSearch3WavesSmall = 16, kSearch3WavesLarge = 4;
 constexpr int64_t kSearch3SmallBatch = 8192;   // boards up to which the small batch's mapping runs
 constexpr int kSearch3MaxKids = 120;           // 2 spawns in at most 4 * 15 slots
 
-__device__ __forceinline__ uint32_t uniform_word(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-
 // what wave 0 leaves for the others
 struct Search3Root {
     uint32_t after[4][4];   // the afterstate of move a, words w0 .. w3
@@ -435,40 +528,45 @@ struct Search3Root {
     uint32_t dealt, done;   // children handed out; children whose leaf is stored
 };
 
-template <int L, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restrict__ boards, int64_t n,
-                                                           const r48::NtLayout lay, const float *__restrict__ tables,
-                                                           int8_t *__restrict__ actions, float *__restrict__ q,
-                                                           uint8_t *__restrict__ legal)
+// Wave 0's part before the barrier: the root's four moves, the slot ballot and the counters, left
+// in LDS for every wave (lane = 16 a + c as depth 2 has it).
+template <int WAVES>
+__device__ __forceinline__ void nt_root_moves(const r48::Board &b, uint32_t lane, Search3Root &root)
 {
-    static_assert(WAVES >= 1 && WAVES <= 16, "a workgroup has at most 1024 lanes");
-    __shared__ float leaf[kSearch3MaxKids];
-    __shared__ Search3Root root;
-    const int64_t i = blockIdx.x;   // the grid has one workgroup per board
-    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t lane = threadIdx.x & 63u, a = lane >> 4, c = lane & 15u;
-    if (w == 0u) {
-        const r48::Board b = r48::load_board(boards, i);
-        const r48::Moves4 m = r48::move_rows4<true>(b);
-        const uint32_t lg = r48::nt_legal4(m, b);
-        const r48::Board s = r48::nt_pick(m, a);
-        const uint64_t M = __ballot(((lg >> a) & 1u) != 0u && r48::nt_cell(s, c) == 0u);
-        if (c == 0u) {
-            root.after[a][0] = s.w0;
-            root.after[a][1] = s.w1;
-            root.after[a][2] = s.w2;
-            root.after[a][3] = s.w3;
-            root.reward[a] = r48::nt_pick_reward(m, a);
-        }
-        if (lane == 0u) {
-            root.legal = lg;
-            root.slots_lo = (uint32_t)M;
-            root.slots_hi = (uint32_t)(M >> 32);
-            root.dealt = (uint32_t)WAVES;   // children 0 .. waves - 1 are dealt by wave number
-            root.done = 0u;
-        }
+    const uint32_t a = lane >> 4, c = lane & 15u;
+    const r48::Moves4 m = r48::move_rows4<true>(b);
+    const uint32_t lg = r48::nt_legal4(m, b);
+    const r48::Board s = r48::nt_pick(m, a);
+    const uint64_t M = __ballot(((lg >> a) & 1u) != 0u && r48::nt_cell(s, c) == 0u);
+    if (c == 0u) {
+        root.after[a][0] = s.w0;
+        root.after[a][1] = s.w1;
+        root.after[a][2] = s.w2;
+        root.after[a][3] = s.w3;
+        root.reward[a] = r48::nt_pick_reward(m, a);
     }
-    __syncthreads();
+    if (lane == 0u) {
+        root.legal = lg;
+        root.slots_lo = (uint32_t)M;
+        root.slots_hi = (uint32_t)(M >> 32);
+        root.dealt = (uint32_t)WAVES;   // children 0 .. waves - 1 are dealt by wave number
+        root.done = 0u;
+    }
+}
+
+// Every wave's part after the barrier, the deal and the finish of the comment above, stated once
+// for both kernels that run it. INNER is the depth a child is searched at: 2 (nt_wave_q2; the
+// board's Q_3, k_nt_search3 and the ruled kernel at depth 3) or 3 (nt_wave_q3 with the wave's LDS
+// slot `keep`; the board's Q_4). Nothing follows it in a kernel: a wave returns from it when it
+// has no more to do.
+template <int L, int WAVES, int INNER>
+__device__ __forceinline__ void nt_deal_and_finish(Search3Root &root, float *leaf, WaveRoot *keep, int64_t i, uint32_t w,
+                                                   uint32_t lane, const r48::NtLayout &lay,
+                                                   const float *__restrict__ tables, int8_t *__restrict__ actions,
+                                                   float *__restrict__ q, uint8_t *__restrict__ legal)
+{
+    static_assert(INNER == 2 || INNER == 3, "a child is searched 2 or 3 plies deep");
+    const uint32_t a = lane >> 4, c = lane & 15u;
     const uint32_t lg = uniform_word(root.legal);
     if (lg == 0u) {   // uniform over the workgroup
         if (w == 0u && lane == 0u) {
@@ -489,13 +587,16 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restr
         const uint32_t *sa = root.after[p >> 4];
         r48::Board child{sa[0], sa[1], sa[2], sa[3]};
         r48::place(child, p & 15u, 1u + (j & 1u), true);
-        uint32_t lg2;
-        const float q2a = nt_wave_q2<L>(child, lane, lay, tables, lg2);
-        // the rows' scores; an illegal reply holds -inf, so the plain max is the max over the legal ones
-        const float b0 = __shfl(q2a, 0), b1 = __shfl(q2a, 16), b2 = __shfl(q2a, 32), b3 = __shfl(q2a, 48);
+        uint32_t lgc;
+        float qc;
+        if constexpr (INNER == 2)
+            qc = nt_wave_q2<L>(child, lane, lay, tables, lgc);
+        else
+            qc = nt_wave_q3<L>(child, lane, lay, tables, keep[w], lgc);
+        const float best = nt_wave_best(qc, lgc);
         uint32_t next = 0u;
         if (lane == 0u) {
-            leaf[j] = lg2 ? fmaxf(fmaxf(b0, b1), fmaxf(b2, b3)) : 0.0f;
+            leaf[j] = best;
             next = __hip_atomic_fetch_add(&root.dealt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         j = uniform_word(next);
@@ -516,6 +617,74 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restr
     if (slot)   // rank2 + 1 < kids <= 120
         x = r48::nt_fma(9.0f, leaf[rank2], leaf[rank2 + 1u]);
     nt_write_search(nt_row_q(x, ok, r, s), lane, lg, i, actions, q, legal);
+}
+
+template <int L, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restrict__ boards, int64_t n,
+                                                           const r48::NtLayout lay, const float *__restrict__ tables,
+                                                           int8_t *__restrict__ actions, float *__restrict__ q,
+                                                           uint8_t *__restrict__ legal)
+{
+    static_assert(WAVES >= 1 && WAVES <= 16, "a workgroup has at most 1024 lanes");
+    __shared__ float leaf[kSearch3MaxKids];
+    __shared__ Search3Root root;
+    const int64_t i = blockIdx.x;   // the grid has one workgroup per board
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    if (w == 0u)
+        nt_root_moves<WAVES>(r48::load_board(boards, i), lane, root);
+    __syncthreads();
+    nt_deal_and_finish<L, WAVES, 2>(root, leaf, nullptr, i, w, lane, lay, tables, actions, q, legal);
+}
+
+// The ruled search of r48_ntuple.h: board i at depth d = rule[blanks(board i)], 1..4, one board per
+// workgroup with k_nt_search3's scheme -- wave 0 makes the root's moves, one barrier, the children
+// dealt from the LDS counter, the last wave to arrive finishes; no waiting loop, nothing shared
+// between workgroups. The depth is uniform over the workgroup (wave 0 leaves it in LDS with the
+// root):
+//   d = 4   a child's leaf is best_3(child), from nt_wave_q3 (each wave with its own LDS slot)
+//   d = 3   best_2(child), from nt_wave_q2: k_nt_search3's body and bits
+//   d <= 2  wave 0 alone runs k_nt_search's depth-2 or depth-1 body on the board it still holds;
+//           the other waves leave after the barrier
+// The rule travels as one word (nt_rule_pack). depth_out[i] = d whether the board has a move or not.
+template <int L, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_nt_search_ruled(const int8_t *__restrict__ boards, int64_t n,
+                                                                const r48::NtLayout lay, const float *__restrict__ tables,
+                                                                const uint64_t rule, int8_t *__restrict__ actions,
+                                                                float *__restrict__ q, uint8_t *__restrict__ legal,
+                                                                uint8_t *__restrict__ depth_out)
+{
+    static_assert(WAVES >= 1 && WAVES <= 16, "a workgroup has at most 1024 lanes");
+    __shared__ float leaf[kSearch3MaxKids];
+    __shared__ Search3Root root;
+    __shared__ WaveRoot keep[WAVES];
+    __shared__ uint32_t depth;
+    const int64_t i = blockIdx.x;   // the grid has one workgroup per board
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    r48::Board b{0u, 0u, 0u, 0u};
+    if (w == 0u) {
+        b = r48::load_board(boards, i);
+        const uint32_t d0 = uniform_word(r48::nt_packed_rule_depth(rule, b));
+        if (d0 >= 3u)
+            nt_root_moves<WAVES>(b, lane, root);
+        if (lane == 0u) {
+            depth = d0;
+            if (depth_out)
+                depth_out[i] = (uint8_t)d0;
+        }
+    }
+    __syncthreads();
+    const uint32_t d = uniform_word(depth);
+    if (d == 4u) {
+        nt_deal_and_finish<L, WAVES, 3>(root, leaf, keep, i, w, lane, lay, tables, actions, q, legal);
+    } else if (d == 3u) {
+        nt_deal_and_finish<L, WAVES, 2>(root, leaf, keep, i, w, lane, lay, tables, actions, q, legal);
+    } else if (w == 0u) {
+        uint32_t lg;
+        const float qa = d == 2u ? nt_wave_q2<L>(b, lane, lay, tables, lg) : nt_wave_q1<L>(b, lane, lay, tables, lg);
+        nt_write_search(qa, lane, lg, i, actions, q, legal);
+    }
 }
 
 // ---- playing whole games: search and env step for n_steps steps in one launch -------------------
@@ -795,6 +964,31 @@ int r48_ntuple_search3(const int8_t *boards, int64_t n, const uint8_t *cells, in
         else
             launch(k_nt_search3<len(), kSearch3WavesLarge>, grid, 64 * kSearch3WavesLarge, stream, boards, n, lay, tables,
                    actions, q, legal);
+    });
+}
+
+int r48_ntuple_search_ruled(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                            const float *tables, const uint8_t *rule, int8_t *actions, float *q, uint8_t *legal,
+                            uint8_t *depth_out, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_args("r48_ntuple_search_ruled", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"actions", actions, 1, true}, {"q", q, 4, false}}))
+        return rc;
+    if (const char *why = r48::nt_rule_check(rule))
+        return fail(R48_EINVAL, std::string("r48_ntuple_search_ruled: bad rule: ") + why);
+    if (n > 0x7FFFFFFFll)   // one board per workgroup
+        return fail(R48_EINVAL, "r48_ntuple_search_ruled: n = " + std::to_string(n) +
+                                    " boards exceed the grid (one per workgroup, 2^31 - 1 workgroups)");
+    const uint64_t packed = r48::nt_rule_pack(rule);
+    const dim3 grid((unsigned)n);
+    return run("k_nt_search_ruled", n, lay.L, [&](auto len) {
+        if (n <= kSearch3SmallBatch)
+            launch(k_nt_search_ruled<len(), kSearch3WavesSmall>, grid, 64 * kSearch3WavesSmall, stream, boards, n, lay,
+                   tables, packed, actions, q, legal, depth_out);
+        else
+            launch(k_nt_search_ruled<len(), kSearch3WavesLarge>, grid, 64 * kSearch3WavesLarge, stream, boards, n, lay,
+                   tables, packed, actions, q, legal, depth_out);
     });
 }
 

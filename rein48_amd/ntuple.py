@@ -60,11 +60,22 @@ _ACT_OUT = (("actions", torch.int8, ()), ("after", torch.int8, (16,)), ("value",
             ("reward", torch.int32, ()), ("legal", torch.uint8, ()))
 _TD_ACT_OUT = _ACT_OUT + (("valid", torch.uint8, ()), ("delta", torch.float32, ()))
 _SEARCH_OUT = (("actions", torch.int8, ()), ("q", torch.float32, (4,)), ("legal", torch.uint8, ()))
+_RULED_OUT = _SEARCH_OUT + (("depth", torch.uint8, ()),)
 
 
 def _outs(spec, given, n, boards):
     """The output tensors of one call in the order of `spec`: the given ones checked, the rest allocated."""
     return tuple(_out(t, name, dtype, (n,) + tail, boards) for t, (name, dtype, tail) in zip(given, spec))
+
+
+def _rule(rule):
+    """A rule of search_ruled as a tuple of 17 ints, each 1..4."""
+    rule = tuple(int(d) for d in rule)
+    if len(rule) != 17:
+        raise ValueError("a rule has 17 depths (blanks 0..16), got %d" % len(rule))
+    if any(not 1 <= d <= 4 for d in rule):
+        raise ValueError("a rule's depths are 1..4, got %r" % (rule,))
+    return rule
 
 
 class NTupleNet:
@@ -198,9 +209,52 @@ class NTupleNet:
                                            _stream(boards)))
         return outs
 
-    def policy(self, depth=1):
+    @staticmethod
+    def depth_rule(d3, d4=-1, base=2):
+        """A rule for search_ruled, a 17-tuple indexed by a board's number of blanks (0..16): 4
+        where blanks <= d4, else 3 where blanks <= d3, else `base` (1..4). depth_rule(16) is three
+        plies everywhere, depth_rule(-1) two; depth_rule(6, 2) searches boards with at most 2 blanks
+        four plies deep, those with 3 to 6 blanks three, the roomier ones two."""
+        base = int(base)
+        if not 1 <= base <= 4:
+            raise ValueError("base depth is 1..4, got %r" % (base,))
+        return tuple(4 if k <= d4 else 3 if k <= d3 else base for k in range(17))
+
+    def search_ruled(self, boards, rule, actions=None, q=None, legal=None, depth=None):
+        """Expectimax at a depth chosen per board -> (actions int8 [n], q float32 [n, 4], legal
+        uint8 [n], depth uint8 [n]). `rule` is 17 depths, each 1..4, indexed by the board's number
+        of blanks (depth_rule builds the usual ones); board i is searched at depth[i] =
+        rule[blanks(board i)] and gets exactly the actions, q and legal of search(depth 1 or 2),
+        of search3 (3), or the same recursion one level deeper (4: a 3-ply search of each of the
+        board's children, then the averaging step). depth is written for every board, one without
+        a legal move included. One launch, one board per workgroup, bitwise reproducible.
+        The rule is the cost guard: a 4-ply search of a roomy board costs about a hundred times
+        its 3-ply search (a board with b blanks has about 2b children per move), so give depth 4
+        to boards with few blanks only. Measured on an MI355X, 4,096 boards of running games,
+        lines-squares / 4x6 (DESIGN.md section 16): three plies everywhere 1.7 / 1.9 ms a call;
+        four plies on the boards with no blank (2 % of them) 2.0 / 2.2 ms, with at most 1 blank
+        (10 %) 3.3 / 3.6 ms, at most 2 (25 %) 6.7 / 7.7 ms, at most 3 (45 %) 13 / 15 ms, at most
+        4 (62 %) 21 / 23 ms. At 2^16 boards a launch stays under 100 ms up to depth_rule(16, 2)
+        (58 / 74 ms) and not beyond (depth_rule(16, 3): 116 / 180 ms): give such rules smaller
+        batches on a shared GPU."""
+        rule = _rule(rule)
+        n = _boards(boards)
+        outs = _outs(_RULED_OUT, (actions, q, legal, depth), n, boards)
+        check(self._lib.r48_ntuple_search_ruled(ptr(boards), n, *self._lay(), ptr(self.tables), (C.c_uint8 * 17)(*rule),
+                                                *map(ptr, outs), _stream(boards)))
+        return outs
+
+    def policy(self, depth=1, rule=None):
         """`policy(boards, t) -> actions` for evaluate.play_episodes: the fused greedy search (depth
-        1, act), the 2-ply expectimax search (depth 2) or the 3-ply one (depth 3, search3)."""
+        1, act), the 2-ply expectimax search (depth 2) or the 3-ply one (depth 3, search3). With a
+        rule (search_ruled: 17 depths 1..4 by the board's blanks) it plays through search_ruled
+        and `depth` is not used."""
+        if rule is not None:
+            rule = _rule(rule)
+
+            def policy(boards, t):
+                return self.search_ruled(boards.contiguous(), rule)[0]
+            return policy
         if depth not in (1, 2, 3):
             raise ValueError("policy depth is 1, 2 or 3, got %r" % (depth,))
         if depth == 1:
@@ -241,17 +295,18 @@ class NTupleNet:
         return boards, length, gain, done
 
     @torch.no_grad()
-    def play_episodes(self, n_boards, seed=0, depth=1, max_steps=20_000, chunk=None, return_scores=False):
+    def play_episodes(self, n_boards, seed=0, depth=1, max_steps=20_000, chunk=None, return_scores=False, rule=None):
         """evaluate.play_episodes(self.policy(depth), n_boards, seed=seed, ...) through play: the
         same dict, every value equal to the last bit except steps_run, which is a multiple of chunk,
         plus mean_gain (the mean sum of merge rewards). The boards are played in launches of `chunk`
-        steps (default PLAY_CHUNK[depth]) with one host check of done in between. depth 3 has no
-        fused kernel and goes to evaluate.play_episodes."""
-        if depth not in (1, 2, 3):
+        steps (default PLAY_CHUNK[depth]) with one host check of done in between. depth 3 and a
+        rule (policy(rule=rule), search_ruled; `depth` is then not used) have no fused kernel and
+        go to evaluate.play_episodes."""
+        if rule is None and depth not in (1, 2, 3):
             raise ValueError("play_episodes depth is 1, 2 or 3, got %r" % (depth,))
-        if depth == 3:
+        if rule is not None or depth == 3:
             from .evaluate import play_episodes
-            return play_episodes(self.policy(3), n_boards, device=self.device, seed=seed, max_steps=max_steps,
+            return play_episodes(self.policy(depth, rule), n_boards, device=self.device, seed=seed, max_steps=max_steps,
                                  return_scores=return_scores)
         chunk = PLAY_CHUNK[depth] if chunk is None else int(chunk)
         if chunk <= 0:
@@ -376,5 +431,5 @@ class NTupleTrainer:
         for _ in range(int(k)):
             self.train_step()
 
-    def policy(self, depth=1):
-        return self.net.policy(depth)
+    def policy(self, depth=1, rule=None):
+        return self.net.policy(depth, rule)

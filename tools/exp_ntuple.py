@@ -6,6 +6,7 @@
     python tools/exp_ntuple.py --search3 [--out DIR] [--sizes 256,4096,16384] [--scores] [--episodes N] [--ab-lib SO]
     python tools/exp_ntuple.py --fused [--out DIR] [--sizes 1024,4096,65536,1048576] [--scores] [--episodes N]
     python tools/exp_ntuple.py --play [--out DIR] [--sizes 4096,65536] [--episodes N] [--ab-lib SO]
+    python tools/exp_ntuple.py --ruled [--out DIR] [--sizes 256,4096,16384] [--scores] [--episodes N]
 
 For both named layouts and each board count: device-event times (5 warm-up calls, median of 7
 windows of 20 calls) of value, act, accumulate and apply with their table loads or atomics per
@@ -69,6 +70,20 @@ search) + env.step in alternated windows; and the device time of single launches
 --ab-lib SO: another build of the library (-DR48_NT_PLAY_LANES=4: four lanes per board at depth 1)
 whose r48_ntuple_play is alternated with this one's, boards compared bit for bit. Writes
 exp_ntuple_play.json.
+
+--ruled: the search at a depth chosen per board (NTupleNet.search_ruled, r48_ntuple_search_ruled). (a)
+For both layouts and each board count (default 256, 4,096 and 2^14): search_ruled under the all-3 rule
+against search3 on the same boards of running games, alternated windows, outputs compared bit for bit
+-- what the shared deal-and-finish body costs over k_nt_search3; --ab-lib SO[,SO...]: other builds
+of the library whose r48_ntuple_search_ruled is alternated with them in the same windows. (b) For both layouts, by rule --
+depth_rule(d3) for d3 = 2, 4, 6, 8, 16 and depth_rule(16, d4) for d4 = 0 .. 4, next to search(2) and
+search3: the time per call at 4,096 boards of running games (alternated windows of 5 calls), the
+share of boards at each depth from depth_out, and the longest of 5 single launches at 2^16 boards.
+With --scores: play_episodes under policy(2), policy(3) and those rules on the recorded recipes'
+tables (lines-squares 1,024 x 2,000 TD(0), 4x6 4,096 x 10,000 TC; --episodes each, eval seed 13; d4
+up to --max-d4, default 3) with the evaluation seconds next to each, and policy(2), policy(3) and
+the rules on the learning test's recipe (lines-squares 1,024 x 1,000, 512 episodes, eval seed 1).
+Writes exp_ntuple_ruled.json.
 """
 import argparse
 import json
@@ -516,6 +531,163 @@ def main_search3(args):
             save()
 
 
+RULES_D3 = (2, 4, 6, 8, 16)
+
+
+def rules_of(max_d4):
+    """{name: rule}: the depth-2/3 mixes, then depth 4 on the crowded boards over depth 3."""
+    rules = {"d3<=%d" % d3: NTupleNet.depth_rule(d3) for d3 in RULES_D3}
+    rules.update({"3,d4<=%d" % d4: NTupleNet.depth_rule(16, d4) for d4 in range(max_d4 + 1)})
+    return rules
+
+
+def random_net(layout):
+    net = NTupleNet(layout, device=DEV)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    net.tables.copy_(torch.randn(net.tables.shape, generator=g, device=DEV) * 30.0)
+    return net
+
+
+def ruled_of_library(path, net):
+    """r48_ntuple_search_ruled of another build of the library, on net's tables."""
+    import ctypes as C
+    from rein48_amd import _lib
+    f = C.CDLL(path).r48_ntuple_search_ruled
+    f.restype, f.argtypes = _lib.SIGNATURES["r48_ntuple_search_ruled"]
+
+    def search_ruled(boards, rule, actions, q, legal, depth):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(f(_lib.ptr(boards), boards.shape[0], *net._lay(), _lib.ptr(net.tables), (C.c_uint8 * 17)(*rule),
+                     _lib.ptr(actions), _lib.ptr(q), _lib.ptr(legal), _lib.ptr(depth), stream))
+    return search_ruled
+
+
+def ruled_all3(layout, n, ab_lib=None):
+    """search_ruled under the all-3 rule against search3: the cost of the shared body."""
+    net = random_net(layout)
+    boards = running_boards(n)
+    a, q, legal = net.search3(boards)
+    ar, qr, lr, dr = net.search_ruled(boards, (3,) * 17)
+    res = {"layout": layout, "boards": n,
+           "bit_equal": bool(torch.equal(qr.view(torch.int32), q.view(torch.int32)) and torch.equal(ar, a) and
+                             torch.equal(lr, legal) and bool((dr == 3).all()))}
+    fns = {"search3": lambda: net.search3(boards, a, q, legal),
+           "ruled_all3": lambda: net.search_ruled(boards, (3,) * 17, ar, qr, lr, dr)}
+    for path in (ab_lib or "").split(","):
+        if not path:
+            continue
+        name = "ruled_all3_" + os.path.splitext(os.path.basename(path))[0]
+        other = ruled_of_library(path, net)
+        outs = tuple(torch.empty_like(x) for x in (ar, qr, lr, dr))
+        other(boards, (3,) * 17, *outs)
+        res[name + "_bit_equal"] = bool(torch.equal(outs[1].view(torch.int32), q.view(torch.int32)) and torch.equal(outs[0], a))
+        fns[name] = lambda other=other, outs=outs: other(boards, (3,) * 17, *outs)
+    for name, t in alternated_ms(fns).items():
+        res[name] = _ms(t)
+    res["ruled_over_search3"] = res["ruled_all3"]["ms"] / res["search3"]["ms"]
+    res["outside_the_spread"] = bool(res["ruled_all3"]["ms_min"] > res["search3"]["ms_max"] or
+                                     res["ruled_all3"]["ms_max"] < res["search3"]["ms_min"])
+    return res
+
+
+def ruled_by_rule(layout, max_d4=4, n=4096, n_big=65536):
+    """Time per call by rule at n boards of running games, the depth shares, the longest launch at n_big."""
+    net = random_net(layout)
+    boards, big = running_boards(n), running_boards(n_big)
+    blanks = (boards == 0).sum(1)
+    res = {"layout": layout, "boards": n, "boards_big": n_big,
+           "blanks_hist": {int(k): float(v) for k, v in enumerate(torch.bincount(blanks, minlength=17).double() / n) if v > 0},
+           "rules": {}}
+    outs = net.search_ruled(boards, (2,) * 17)
+    outs_big = net.search_ruled(big, (2,) * 17)
+    fns = {"search2": lambda: net.search(boards, 2, *outs[:3]), "search3": lambda: net.search3(boards, *outs[:3])}
+    big_fns = {"search2": lambda: net.search(big, 2, *outs_big[:3]), "search3": lambda: net.search3(big, *outs_big[:3])}
+    rules = rules_of(max_d4)
+    for name, rule in rules.items():
+        fns[name] = lambda rule=rule: net.search_ruled(boards, rule, *outs)
+        big_fns[name] = lambda rule=rule: net.search_ruled(big, rule, *outs_big)
+    times = alternated_ms(fns, warmup=2, windows=7, calls=5)
+    for name in fns:
+        row = _ms(times[name])
+        rule = rules.get(name, (2,) * 17 if name == "search2" else (3,) * 17)
+        d = net.search_ruled(boards, rule, *outs)[3]
+        row["share_by_depth"] = {int(k): float(v) for k, v in enumerate(torch.bincount(d.long(), minlength=5).double() / n) if v > 0}
+        launches = []
+        for _ in range(6):                                               # the first is the warm-up
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            big_fns[name]()
+            e1.record()
+            torch.cuda.synchronize()
+            launches.append(e0.elapsed_time(e1))
+        row["longest_launch_ms_big"] = max(launches[1:])
+        row["rule"] = list(rule)
+        res["rules"][name] = row
+    return res
+
+
+def ruled_scores(layout, n_boards, steps, alpha, tc, eval_seed, episodes, max_d4):
+    tr = NTupleTrainer(NTupleConfig(n_boards=n_boards, layout=layout, alpha=alpha, seed=0, tc=tc, fused=True), device=DEV)
+    for _ in range(steps):
+        tr.train_step()
+    torch.cuda.synchronize()
+    out = {"layout": layout, "train_boards": n_boards, "train_steps": steps, "alpha": alpha, "tc": tc,
+           "eval_seed": eval_seed, "episodes": episodes, "policies": {}}
+    policies = {"depth2": tr.policy(depth=2), "depth3": tr.policy(depth=3)}
+    rules = rules_of(max_d4)
+    policies.update({name: tr.policy(rule=rule) for name, rule in rules.items() if name != "d3<=16"})
+    for name, policy in policies.items():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ev = play_episodes(policy, episodes, device=DEV, seed=eval_seed, return_scores=True)
+        torch.cuda.synchronize()
+        sc = ev.pop("scores").numpy()
+        ev["score_std"] = float(sc.std(ddof=1))
+        ev["standard_error"] = ev["score_std"] / episodes ** 0.5
+        ev["eval_seconds"] = time.perf_counter() - t0
+        ev.pop("max_tile_exponent_hist")
+        out["policies"][name] = ev
+        print(json.dumps({layout: name, "mean_score": ev["mean_score"], "se": ev["standard_error"],
+                          "eval_seconds": ev["eval_seconds"]}), flush=True)
+    base = out["policies"]["depth3"]
+    for name, ev in out["policies"].items():
+        se = (ev["standard_error"] ** 2 + base["standard_error"] ** 2) ** 0.5
+        ev["over_depth3_in_standard_errors"] = (ev["mean_score"] - base["mean_score"]) / se
+        ev["seconds_over_depth3"] = ev["eval_seconds"] / base["eval_seconds"]
+    del tr
+    torch.cuda.empty_cache()
+    return out
+
+
+def main_ruled(args):
+    out = {"device": torch.cuda.get_device_name(0), "all3": [], "by_rule": [], "scores": []}
+
+    def save():
+        if args.out:
+            os.makedirs(args.out, exist_ok=True)
+            with open(os.path.join(args.out, "exp_ntuple_ruled.json"), "w") as f:
+                json.dump(out, f, indent=1)
+    for layout in ("lines-squares", "4x6"):
+        for n in (int(s) for s in (args.sizes or "256,4096,16384").split(",")):
+            r = ruled_all3(layout, n, args.ab_lib)
+            out["all3"].append(r)
+            print(json.dumps(r), flush=True)
+    save()
+    for layout in ("lines-squares", "4x6"):
+        r = ruled_by_rule(layout)
+        out["by_rule"].append(r)
+        print(json.dumps(r), flush=True)
+        save()
+    if args.scores:
+        for layout, n_boards, steps, alpha, tc, seed, episodes in (
+                ("lines-squares", 1024, 1000, 0.25, False, 1, 512), ("lines-squares", 1024, 2000, 0.25, False, 13, args.episodes),
+                ("4x6", 4096, 10000, 1.0, True, 13, args.episodes)):
+            r = ruled_scores(layout, n_boards, steps, alpha, tc, seed, episodes, args.max_d4)
+            out["scores"].append(r)
+            print(json.dumps(r), flush=True)
+            save()
+
+
 def alternated_host_ms(fns, warmup=20, windows=7, calls=20):
     """alternated_ms on the host clock: every window is `calls` calls and a synchronise, as a
     training loop pays for them -- ({name: the windows' times in order}, {name: the median time
@@ -899,9 +1071,13 @@ def main():
     ap.add_argument("--play", action="store_true")
     ap.add_argument("--episodes", type=int, default=4096)
     ap.add_argument("--ab-lib", default=None)
+    ap.add_argument("--ruled", action="store_true")
+    ap.add_argument("--max-d4", type=int, default=3)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("exp_ntuple.py needs a GPU")
+    if args.ruled:
+        return main_ruled(args)
     if args.play:
         return main_play(args)
     if args.fused:
