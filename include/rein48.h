@@ -699,6 +699,29 @@ int r48_ntuple_play(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, 
                     int32_t depth, int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step,
                     int32_t *length, int32_t *gain, uint8_t *done, void *stream);
 
+/* Whole games in one launch at a search depth chosen per board and per step, 1..4 plies. As
+ * r48_ntuple_play with the ruled search choosing the move: for t = 0 .. n_steps - 1, board i
+ *   1. takes the action r48_ntuple_search_ruled returns for its current board under rule (uint8[17]
+ *      ON THE HOST, every entry in 1..4; the depth is rule[the board's number of zero cells], so it
+ *      follows the game), then
+ *   2. makes the step of r48_ntuple_play: r48_env_step(actions, flags = 0) on an env with seed
+ *      env_seed, global board id gid0 + i and step counter env_step + t (uint32, it wraps), draw
+ *      contract 3, no auto-reset.
+ * boards, length (in/out, +=), gain (in/out, +=) and done are r48_ntuple_play's, each of the last
+ * three nullable; the caller advances the env's step counter by n_steps. Everything equals n_steps x
+ * (r48_ntuple_search_ruled, r48_env_step) bit for bit, for every n, gid0, env_step and rule. One
+ * board per workgroup, which stays on its board for all n_steps: a step at depth 3 or 4 deals the
+ * board's children to the workgroup's waves, a step at depth 1 or 2 runs on one wave; a board
+ * without a legal move is finished and its workgroup leaves. The cost guard of
+ * r48_ntuple_search_ruled applies to every step: keep depth 4 to boards with few blanks and n_steps
+ * small enough for the launch to stay short. R48_EINVAL (before any HIP call) as r48_ntuple_value,
+ * and for NULL tables, tables / length / gain not 4-byte aligned, a NULL rule, a rule entry outside
+ * 1..4, n_steps < 0, or n beyond 2^31 - 1 boards (the grid). n == 0 or n_steps == 0 is a no-op
+ * after these checks. r48_ntuple_play itself keeps refusing depth 3. */
+int r48_ntuple_play_ruled(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                          const uint8_t *rule, int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step,
+                          int32_t *length, int32_t *gain, uint8_t *done, void *stream);
+
 /* The TD update in two launches, both over the hits (i, t, g) of the boards with valid[i] != 0
  * (valid NULL: all). Scratch: acc int64[m][16^L], cnt uint32[m][16^L], which MUST BE ALL ZERO ON
  * ENTRY to r48_ntuple_accumulate (r48_ntuple_apply leaves them zero again).

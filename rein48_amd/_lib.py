@@ -140,7 +140,8 @@ SIGNATURES = {
     "r48_ntuple_search3": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     "r48_ntuple_search_ruled": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "r48_ntuple_play": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _I32, _U64, _I64, _U32, _P, _P, _P, _P]),
-    "r48_ntuple_accumulate": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "r48_ntuple_play_ruled": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _I32, _U64, _I64, _U32, _P, _P, _P, _P]),
+    "r48_ntuple_accumulate":(C.c_int, [_P, _I64, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "r48_ntuple_apply": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P]),
     "r48_ntuple_apply_tc": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P, _P, _P]),
     "r48_ntuple_tc_rate": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _P]),

@@ -581,4 +581,34 @@ inline void nt_play_board(Board &board, const NtLayout &lay, const float *tables
     }
 }
 
+// The ruled play contract (k_nt_play_ruled, and nt_play_board_ruled for one board on the host): the
+// play contract above with the ruled search choosing the move. For t = 0 .. n_steps - 1 the board
+//   1. takes the action of the ruled search of its CURRENT board: nt_search_board_ruled under
+//      `rule`, i.e. the search at depth rule[blanks(board)], 1..4 -- the depth follows the game,
+//   2. makes nt_play_step with it: draw contract 3 as board `gid` at step counter step0 + t (uint32,
+//      it wraps), no auto-reset.
+// length, gain and done mean what they mean above: length and gain are added to, so chunked calls
+// add up, done is nt_play_done of the final board, and a board without a legal move is finished:
+// every later step is the identity on it, whatever its depth. Everything equals n_steps x
+// (r48_ntuple_search_ruled, r48_env_step) bit for bit, for every n, gid, step0 and rule; the bits
+// depend neither on the number of waves that share a board nor on how its children were dealt.
+template <int L>
+inline void nt_play_board_ruled(Board &board, const NtLayout &lay, const float *tables, const uint8_t *rule, int n_steps,
+                                uint32_t k0, uint32_t k1, uint64_t gid, uint32_t step0, int32_t *length, int32_t *gain,
+                                uint8_t *done)
+{
+    for (int t = 0; t < n_steps; t++) {
+        float q[4];
+        uint32_t legal;
+        const uint32_t action = nt_search_board_ruled<L>(board, lay, tables, rule, q, legal, nullptr);
+        const StepOut o = nt_play_step(board, action, gid, step0 + (uint32_t)t, k0, k1);
+        if (length)
+            *length += (int32_t)o.changed;
+        if (gain)
+            *gain += (int32_t)o.reward;
+        if (done)
+            *done = (uint8_t)o.done;
+    }
+}
+
 }  // namespace r48

@@ -17,15 +17,18 @@
 //   nt_root_moves,   one board per workgroup: wave 0's root      k_nt_search3, k_nt_search_ruled
 //   nt_deal_and_     moves, then children dealt from an LDS
 //   finish           counter and finished by the last wave
+//   nt_child_best,   one dealt child searched by a wave; the     nt_deal_and_finish, k_nt_play_ruled
+//   nt_finish_rows   finishing row step over the stored leaves
 //   nt_row_q,        how a search ends: butterfly, Q, the four   nt_wave_q2, nt_wave_q3, k_nt_search,
-//   nt_write_search  rows' scores, argmax, the writes            nt_deal_and_finish
+//   nt_write_search  rows' scores, argmax, the writes            nt_finish_rows / nt_deal_and_finish
 //   nt_play_store    what a played board leaves behind           k_nt_play1 (over nt_act_board),
-//                                                                k_nt_play2 (over nt_wave_q2)
+//                                                                k_nt_play2 (over nt_wave_q2),
+//                                                                k_nt_play_ruled (over the ruled search)
 // and r48_ntuple.h's nt_value (k_nt_value and everything above) and nt_tc_rate_mean (k_nt_tc_rate).
 // k_nt_td_act is act, the trainer's TD error and accumulate for the previous step's afterstates in
-// one launch: the fused training step. k_nt_search runs one board per WAVE, k_nt_search3 and
-// k_nt_search_ruled one per WORKGROUP; every other kernel one board per lane with one 16-byte
-// board load. All are templated on the tuple length L so the cell loops unroll; the expanded
+// one launch: the fused training step. k_nt_search runs one board per WAVE, k_nt_search3,
+// k_nt_search_ruled and k_nt_play_ruled one per WORKGROUP; every other kernel one board per lane
+// with one 16-byte board load. All are templated on the tuple length L so the cell loops unroll; the expanded
 // layout travels by value in the kernel arguments (wave-uniform).
 #include <hip/hip_runtime.h>
 
@@ -554,6 +557,47 @@ __device__ __forceinline__ void nt_root_moves(const r48::Board &b, uint32_t lane
     }
 }
 
+// One dealt child, by a whole wave: the root's child j (spawn 1 + (j & 1) in the slot
+// nt_select_bit(M, j >> 1), its parent afterstate read from `root` with a uniform address) searched
+// INNER plies deep -- 2: nt_wave_q2, 3: nt_wave_q3 with the wave's own LDS slot -- and best_INNER of
+// it in every lane. The per-child body of nt_deal_and_finish and of k_nt_play_ruled.
+template <int L, int INNER>
+__device__ __forceinline__ float nt_child_best(const Search3Root &root, uint64_t M, uint32_t j, uint32_t lane,
+                                               const r48::NtLayout &lay, const float *__restrict__ tables,
+                                               WaveRoot *keep_w)
+{
+    static_assert(INNER == 2 || INNER == 3, "a child is searched 2 or 3 plies deep");
+    const uint32_t p = r48::nt_select_bit(M, j >> 1);   // < 64
+    const uint32_t *sa = root.after[p >> 4];
+    r48::Board child{sa[0], sa[1], sa[2], sa[3]};
+    r48::place(child, p & 15u, 1u + (j & 1u), true);
+    uint32_t lgc;
+    float qc;
+    if constexpr (INNER == 2)
+        qc = nt_wave_q2<L>(child, lane, lay, tables, lgc);
+    else
+        qc = nt_wave_q3<L>(child, lane, lay, tables, *keep_w, lgc);
+    return nt_wave_best(qc, lgc);
+}
+
+// The finishing row step, by one wave once every leaf is stored: the slot lane of rank rho reads
+// leaf[2 rho] and leaf[2 rho + 1] -- by child number, so the deal does not reach the bits -- forms
+// x_c by nt_fma, and nt_row_q gives the lane its row's Q. Shared like nt_child_best.
+__device__ __forceinline__ float nt_finish_rows(const Search3Root &root, const float *leaf, uint64_t M, uint32_t lg,
+                                                uint32_t lane)
+{
+    const uint32_t a = lane >> 4;
+    const r48::Board s{root.after[a][0], root.after[a][1], root.after[a][2], root.after[a][3]};
+    const uint32_t r = root.reward[a];
+    const bool ok = ((lg >> a) & 1u) != 0u;
+    const bool slot = ((M >> lane) & 1ull) != 0ull;
+    const uint32_t rank2 = 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
+    float x = 0.0f;
+    if (slot)   // rank2 + 1 < kids <= 120
+        x = r48::nt_fma(9.0f, leaf[rank2], leaf[rank2 + 1u]);
+    return nt_row_q(x, ok, r, s);
+}
+
 // Every wave's part after the barrier, the deal and the finish of the comment above, stated once
 // for both kernels that run it. INNER is the depth a child is searched at: 2 (nt_wave_q2; the
 // board's Q_3, k_nt_search3 and the ruled kernel at depth 3) or 3 (nt_wave_q3 with the wave's LDS
@@ -583,17 +627,7 @@ __device__ __forceinline__ void nt_deal_and_finish(Search3Root &root, float *lea
     uint32_t mine = 0u;
 #pragma unroll 1
     for (uint32_t j = w; j < kids; mine++) {
-        const uint32_t p = r48::nt_select_bit(M, j >> 1);   // < 64
-        const uint32_t *sa = root.after[p >> 4];
-        r48::Board child{sa[0], sa[1], sa[2], sa[3]};
-        r48::place(child, p & 15u, 1u + (j & 1u), true);
-        uint32_t lgc;
-        float qc;
-        if constexpr (INNER == 2)
-            qc = nt_wave_q2<L>(child, lane, lay, tables, lgc);
-        else
-            qc = nt_wave_q3<L>(child, lane, lay, tables, keep[w], lgc);
-        const float best = nt_wave_best(qc, lgc);
+        const float best = nt_child_best<L, INNER>(root, M, j, lane, lay, tables, keep + w);
         uint32_t next = 0u;
         if (lane == 0u) {
             leaf[j] = best;
@@ -608,15 +642,7 @@ __device__ __forceinline__ void nt_deal_and_finish(Search3Root &root, float *lea
         before = __hip_atomic_fetch_add(&root.done, mine, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (uniform_word(before) + mine != kids)
         return;
-    const r48::Board s{root.after[a][0], root.after[a][1], root.after[a][2], root.after[a][3]};
-    const uint32_t r = root.reward[a];
-    const bool ok = ((lg >> a) & 1u) != 0u;
-    const bool slot = ((M >> lane) & 1ull) != 0ull;
-    const uint32_t rank2 = 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
-    float x = 0.0f;
-    if (slot)   // rank2 + 1 < kids <= 120
-        x = r48::nt_fma(9.0f, leaf[rank2], leaf[rank2 + 1u]);
-    nt_write_search(nt_row_q(x, ok, r, s), lane, lg, i, actions, q, legal);
+    nt_write_search(nt_finish_rows(root, leaf, M, lg, lane), lane, lg, i, actions, q, legal);
 }
 
 template <int L, int WAVES>
@@ -815,6 +841,169 @@ __global__ __launch_bounds__(kBlock) void k_nt_play2(int8_t *__restrict__ boards
         gn += o.reward;
     }
     if (lane == 0u)
+        nt_play_store(boards, i, b, len, gn, length, gain, done);
+}
+
+// The ruled play contract of r48_ntuple.h: every step searches the board at rule[its blanks] plies.
+// One board per workgroup of WAVES waves, as k_nt_search_ruled, and the workgroup stays on its board
+// for all n_steps. EVERY wave holds the board and the step number t in registers, the same bits in
+// all of them, and the loop below keeps it so; a step is one of two PHASES, chosen by the depth d of
+// the board -- a function of those registers, hence the same in every wave:
+//   d >= 3  a DEEP step. Wave 0 makes the root's moves into root[par] (nt_root_moves); barrier B1;
+//           every wave reads the legal set and the slot ballot from there and the children are dealt
+//           from the LDS counter, best_(d-1)(child j) to leaf[par][j] (nt_child_best); barrier B2 is
+//           the hand-over that nt_deal_and_finish does by counting arrivals, since here the waves go
+//           on; then EVERY wave runs the finishing row step (nt_finish_rows: the same LDS words, the
+//           same arithmetic, so the same four scores), takes the first maximiser and makes the env's
+//           step on its own copy of the board. Nothing is handed back: the copies stay equal.
+//   d <= 2  a SHALLOW run. Wave 0 alone plays on -- nt_wave_q2 / nt_wave_q1 and the step, as
+//           k_nt_play2 does -- for as long as the board stays at depth <= 2, has a move and steps
+//           are left, then leaves the board, t and whether it still has a move in hand[hpar];
+//           barrier B0; the other waves, which came straight to B0, take them from there.
+// The barriers. A wave's path through the loop is decided by t < n_steps, d and, after a barrier,
+// by two LDS words: root[par].legal (game over at a deep step) and hand[hpar].alive (at a shallow
+// run). t and the board are equal registers in every wave (by induction: both phases leave them
+// equal), and each of the two words is written by wave 0 BEFORE the barrier it is read after and not
+// again until wave 0 has passed two more barriers (below), so no wave can read another value of it:
+// every condition that guards a barrier is workgroup-uniform by construction, and all waves make
+// the same sequence of B0 / B1 / B2 and leave the loop together.
+// The buffers. root / leaf and hand are double-buffered by the parity of the deep steps (par) and of
+// the shallow runs (hpar), which every wave counts alike. A deep step's buffers are last read in its
+// finishing step, i.e. before the reader arrives at its next barrier; wave 0 writes the same parity
+// again two deep steps later, after it has passed B1 and B2 of the step in between, which no wave
+// passes before every wave has arrived there. The same holds for hand with the B0 of the run in
+// between (and a shallow run is in fact always followed by a deep step or the end). So no second
+// barrier per phase is needed to protect leaf[], the counters or the hand-over words.
+// length and gain are wave 0's sums (it makes every step); lane 0 of wave 0 stores once.
+// Waves per board: 16 up to 8,192 boards and 4 beyond, as k_nt_search_ruled. Measured (DESIGN.md,
+// profiles/ntuple/exp_ntuple_play_ruled_waves.json): 8 waves take 4 to 6 % less than 16 for 4,096
+// depth-3 evaluations but 14 to 17 % more under depth_rule(16, 1) and 1.4x at 64 boards, where a
+// board's own latency is what counts; 4 waves lose everywhere up to 8,192 boards and win beyond.
+// R48_NT_PLAY_RULED_WAVES (an experiment's build) fixes one number of waves for every n; the bits do
+// not depend on it.
+#ifdef R48_NT_PLAY_RULED_WAVES
+constexpr int kPlayRuledWavesSmall = R48_NT_PLAY_RULED_WAVES, kPlayRuledWavesLarge = R48_NT_PLAY_RULED_WAVES;
+#else
+constexpr int kPlayRuledWavesSmall = 16, kPlayRuledWavesLarge = 4;
+#endif
+
+// A board whose words are the same in every lane, as scalars: what is carried from step to step
+// lives in SGPRs and takes no vector register across a search.
+__device__ __forceinline__ r48::Board uniform_board(const r48::Board &b)
+{
+    return r48::Board{uniform_word(b.w0), uniform_word(b.w1), uniform_word(b.w2), uniform_word(b.w3)};
+}
+
+// what wave 0 leaves for the others after a shallow run
+struct PlayHand {
+    uint32_t board[4];
+    uint32_t t, alive;
+};
+
+template <int L, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_nt_play_ruled(int8_t *__restrict__ boards, int64_t n,
+                                                              const r48::NtLayout lay, const float *__restrict__ tables,
+                                                              const uint64_t rule, int32_t n_steps, uint32_t k0,
+                                                              uint32_t k1, int64_t gid0, uint32_t step0,
+                                                              int32_t *__restrict__ length, int32_t *__restrict__ gain,
+                                                              uint8_t *__restrict__ done)
+{
+    static_assert(WAVES >= 1 && WAVES <= 16, "a workgroup has at most 1024 lanes");
+    __shared__ float leaf[2][kSearch3MaxKids];
+    __shared__ Search3Root root[2];
+    __shared__ WaveRoot keep[WAVES];
+    __shared__ PlayHand hand[2];
+    const int64_t i = blockIdx.x;   // the grid has one workgroup per board
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t gid = (uint64_t)(gid0 + i);
+    r48::Board b = uniform_board(r48::load_board(boards, i));   // every wave, the same address
+    uint32_t len = 0u, gn = 0u, par = 0u, hpar = 0u;
+    uint32_t t = 0u;
+    const uint32_t steps = (uint32_t)n_steps;    // > 0, the entry point returns before the launch otherwise
+#pragma unroll 1
+    while (t < steps) {   // uniform over the workgroup: t is
+        uint32_t d = uniform_word(r48::nt_packed_rule_depth(rule, b));
+        if (d <= 2u) {    // uniform over the workgroup: the board is
+            PlayHand &h = hand[hpar];
+            hpar ^= 1u;
+            if (w == 0u) {
+                uint32_t alive = 1u;
+#pragma unroll 1
+                do {
+                    uint32_t lg;
+                    const float qa = d == 2u ? nt_wave_q2<L>(b, lane, lay, tables, lg) : nt_wave_q1<L>(b, lane, lay, tables, lg);
+                    if (uniform_word(lg) == 0u) {
+                        alive = 0u;   // finished
+                        break;
+                    }
+                    const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
+                    const r48::StepOut o = r48::nt_play_step(b, r48::nt_argmax4(q0, q1, q2, q3), gid, step0 + t, k0, k1);
+                    b = uniform_board(b);
+                    len += uniform_word(o.changed);
+                    gn += uniform_word(o.reward);
+                    t++;
+                    d = uniform_word(r48::nt_packed_rule_depth(rule, b));
+                } while (t < steps && d <= 2u);
+                if (lane == 0u) {
+                    h.board[0] = b.w0;
+                    h.board[1] = b.w1;
+                    h.board[2] = b.w2;
+                    h.board[3] = b.w3;
+                    h.t = t;
+                    h.alive = alive;
+                }
+            }
+            // B0. Reached by every wave: the branch above is taken on d and t, equal in all of them, and
+            // the only code that skips ahead inside it is wave 0's own loop, which ends here too.
+            __syncthreads();
+            b = uniform_board(r48::Board{h.board[0], h.board[1], h.board[2], h.board[3]});
+            t = uniform_word(h.t);
+            // h was written before B0 and is not written again before two more barriers: every wave
+            // reads the same alive, and all leave or none
+            if (uniform_word(h.alive) == 0u)
+                break;
+            continue;
+        }
+        Search3Root &rt = root[par];
+        float *lf = leaf[par];
+        par ^= 1u;
+        if (w == 0u)
+            nt_root_moves<WAVES>(b, lane, rt);
+        // B1. Reached by every wave: nothing between the loop's head and here depends on anything but
+        // t and d.
+        __syncthreads();
+        // rt.legal was written before B1 and is not written again before wave 0 has passed B2 and the
+        // barriers of the next deep step: every wave reads the same set, and all leave or none
+        const uint32_t lg = uniform_word(rt.legal);
+        if (lg == 0u)
+            break;   // finished
+        const uint64_t M = (uint64_t)uniform_word(rt.slots_lo) | ((uint64_t)uniform_word(rt.slots_hi) << 32);
+        const uint32_t kids = 2u * (uint32_t)__popcll(M);   // 4 .. 120
+#pragma unroll 1
+        for (uint32_t j = w; j < kids;) {   // a wave's own loop: it ends at B2 however many children it took, none included
+            const float best = d == 4u ? nt_child_best<L, 3>(rt, M, j, lane, lay, tables, keep + w)
+                                       : nt_child_best<L, 2>(rt, M, j, lane, lay, tables, keep + w);
+            uint32_t next = 0u;
+            if (lane == 0u) {
+                lf[j] = best;   // j < kids <= kSearch3MaxKids
+                next = __hip_atomic_fetch_add(&rt.dealt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            j = uniform_word(next);
+        }
+        // B2, the hand-over: every leaf is stored before it, every wave reads them after it. Reached by
+        // every wave: the break above is uniform (lg), the deal loop is left by every wave in the end,
+        // and there is no other way out of this step.
+        __syncthreads();
+        const float qa = nt_finish_rows(rt, lf, M, lg, lane);
+        const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
+        const r48::StepOut o = r48::nt_play_step(b, r48::nt_argmax4(q0, q1, q2, q3), gid, step0 + t, k0, k1);
+        b = uniform_board(b);
+        len += uniform_word(o.changed);
+        gn += uniform_word(o.reward);
+        t++;
+    }
+    if (w == 0u && lane == 0u)
         nt_play_store(boards, i, b, len, gn, length, gain, done);
 }
 
@@ -1020,6 +1209,36 @@ int r48_ntuple_play(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, 
         else
             launch(k_nt_play2<len()>, grid, kBlock, stream, boards, n, lay, tables, n_steps, k0, k1, gid0, env_step, length,
                    gain, done);
+    });
+}
+
+int r48_ntuple_play_ruled(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                          const uint8_t *rule, int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step,
+                          int32_t *length, int32_t *gain, uint8_t *done, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_args("r48_ntuple_play_ruled", boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"length", length, 4, false}, {"gain", gain, 4, false}}))
+        return rc;
+    if (const char *why = r48::nt_rule_check(rule))
+        return fail(R48_EINVAL, std::string("r48_ntuple_play_ruled: bad rule: ") + why);
+    if (n_steps < 0)
+        return fail(R48_EINVAL, "r48_ntuple_play_ruled: n_steps must not be negative, got " + std::to_string(n_steps));
+    if (n > 0x7FFFFFFFll)   // one board per workgroup
+        return fail(R48_EINVAL, "r48_ntuple_play_ruled: n = " + std::to_string(n) +
+                                    " boards exceed the grid (one per workgroup, 2^31 - 1 workgroups)");
+    if (n_steps == 0)
+        return R48_OK;
+    const uint64_t packed = r48::nt_rule_pack(rule);
+    const dim3 grid((unsigned)n);
+    const uint32_t k0 = (uint32_t)env_seed, k1 = (uint32_t)(env_seed >> 32);
+    return run("k_nt_play_ruled", n, lay.L, [&](auto len) {
+        if (n <= kSearch3SmallBatch)
+            launch(k_nt_play_ruled<len(), kPlayRuledWavesSmall>, grid, 64 * kPlayRuledWavesSmall, stream, boards, n, lay,
+                   tables, packed, n_steps, k0, k1, gid0, env_step, length, gain, done);
+        else
+            launch(k_nt_play_ruled<len(), kPlayRuledWavesLarge>, grid, 64 * kPlayRuledWavesLarge, stream, boards, n, lay,
+                   tables, packed, n_steps, k0, k1, gid0, env_step, length, gain, done);
     });
 }
 

@@ -39,6 +39,23 @@ LAYOUTS = {
 # on an MI355X (DESIGN.md section 16 has the measured launch times)
 PLAY_CHUNK = {1: 1000, 2: 100}
 
+# board-steps per launch of play_ruled in play_episodes, by the rule's largest depth: a launch with
+# every board alive stays under 100 ms on an MI355X (DESIGN.md "Whole games at a per-board depth"
+# has the measured launch times: at 4,096 boards 25 ms, 29 ms, 74 ms from reset at depths 1, 2, 3 and
+# 33 ms under depth_rule(16, 3), the costliest rule recorded, which depth 4 is sized for; a rule
+# with depth 4 on roomier boards takes longer per step, in play_ruled as in search_ruled).
+RULED_BUDGET = {1: 1 << 20, 2: 1 << 18, 3: 1 << 16, 4: 1 << 13}
+# and the most steps per launch: with few boards a launch costs its steps times ONE board's step
+# (~0.1 ms at depth 3: 1,024 steps of 64 boards measured 100 ms)
+RULED_MAX_CHUNK = {1: 4096, 2: 1024, 3: 512, 4: 16}
+
+
+def ruled_chunk(max_depth, n_boards):
+    """Steps per launch of play_ruled in play_episodes: RULED_BUDGET[max_depth] board-steps over
+    n_boards, at least 1 step and at most RULED_MAX_CHUNK[max_depth]."""
+    d = int(max_depth)
+    return max(1, min(RULED_BUDGET[d] // max(1, int(n_boards)), RULED_MAX_CHUNK[d]))
+
 
 def layout_cells(layout):
     """A layout name or a sequence of equal-length cell tuples -> tuple of tuples of ints."""
@@ -275,40 +292,74 @@ class NTupleNet:
         them (no auto-reset), bit for bit, so a following env.step draws the same spawns. length +=
         the steps that changed a board, gain += their merge rewards: pass the tensors of an earlier
         call and chunked calls add up (allocated zero where None). A board without a legal move is
-        finished and costs nothing more; a wave stops once all its boards are. depth 1 or 2."""
+        finished and costs nothing more; a wave stops once all its boards are. depth 1 or 2; play_ruled
+        plays at depth 3 and under a rule."""
         if depth not in (1, 2):
-            raise ValueError("play depth is 1 or 2, got %r (three plies: play_episodes)" % (depth,))
+            raise ValueError("play depth is 1 or 2, got %r (three plies and rules: play_ruled)" % (depth,))
         boards = env.boards
         if boards.device != self.device:
             raise ValueError("the env is on %s, the net on %s" % (boards.device, self.device))
         n = _boards(boards)
         n_steps = int(n_steps)
-        length = torch.zeros(n, dtype=torch.int32, device=self.device) if length is None else length
-        gain = torch.zeros(n, dtype=torch.int32, device=self.device) if gain is None else gain
-        length, gain = _out(length, "length", torch.int32, (n,), boards), _out(gain, "gain", torch.int32, (n,), boards)
-        done = torch.zeros(n, dtype=torch.uint8, device=self.device) if done is None else done
-        done = _out(done, "done", torch.uint8, (n,), boards)      # n_steps == 0 leaves it as it is
+        length, gain, done = self._play_outs(n, boards, length, gain, done)
         step, reset = env.counters
         check(self._lib.r48_ntuple_play(ptr(boards), n, *self._lay(), ptr(self.tables), depth, n_steps, env.seed,
                                         env.board_offset, step, ptr(length), ptr(gain), ptr(done), _stream(boards)))
         env.counters = ((step + n_steps) & 0xFFFFFFFF, reset)
         return boards, length, gain, done
 
+    def play_ruled(self, env, n_steps, rule, length=None, gain=None, done=None):
+        """n_steps x (policy(rule=rule), env.step) on env's boards in ONE launch -> (boards, length
+        int32 [n], gain int32 [n], done uint8 [n]), play's tuple with play's meaning: every step
+        searches a board at rule[its number of blanks] plies (1..4; depth_rule builds the usual
+        rules, (3,) * 17 is three plies throughout), so the depth follows the game. The boards,
+        done and env.counters end exactly where n_steps calls of env.step(self.search_ruled(boards,
+        rule)[0]) leave them (no auto-reset), bit for bit; length and gain add up over chunked
+        calls. One board per workgroup, which stays on it for all n_steps; a board without a legal
+        move is finished and costs nothing more. search_ruled's cost guard applies to every step:
+        keep depth 4 to boards with few blanks and n_steps small (play_episodes' chunks keep a
+        launch under 100 ms)."""
+        rule = _rule(rule)
+        boards = env.boards
+        if boards.device != self.device:
+            raise ValueError("the env is on %s, the net on %s" % (boards.device, self.device))
+        n = _boards(boards)
+        n_steps = int(n_steps)
+        length, gain, done = self._play_outs(n, boards, length, gain, done)
+        step, reset = env.counters
+        check(self._lib.r48_ntuple_play_ruled(ptr(boards), n, *self._lay(), ptr(self.tables), (C.c_uint8 * 17)(*rule),
+                                              n_steps, env.seed, env.board_offset, step, ptr(length), ptr(gain),
+                                              ptr(done), _stream(boards)))
+        env.counters = ((step + n_steps) & 0xFFFFFFFF, reset)
+        return boards, length, gain, done
+
+    def _play_outs(self, n, boards, length, gain, done):
+        """play's in/out tensors: the given ones checked, zeros where None."""
+        length = torch.zeros(n, dtype=torch.int32, device=self.device) if length is None else length
+        gain = torch.zeros(n, dtype=torch.int32, device=self.device) if gain is None else gain
+        length, gain = _out(length, "length", torch.int32, (n,), boards), _out(gain, "gain", torch.int32, (n,), boards)
+        done = torch.zeros(n, dtype=torch.uint8, device=self.device) if done is None else done
+        return length, gain, _out(done, "done", torch.uint8, (n,), boards)      # n_steps == 0 leaves done as it is
+
     @torch.no_grad()
     def play_episodes(self, n_boards, seed=0, depth=1, max_steps=20_000, chunk=None, return_scores=False, rule=None):
-        """evaluate.play_episodes(self.policy(depth), n_boards, seed=seed, ...) through play: the
-        same dict, every value equal to the last bit except steps_run, which is a multiple of chunk,
-        plus mean_gain (the mean sum of merge rewards). The boards are played in launches of `chunk`
-        steps (default PLAY_CHUNK[depth]) with one host check of done in between. depth 3 and a
-        rule (policy(rule=rule), search_ruled; `depth` is then not used) have no fused kernel and
-        go to evaluate.play_episodes."""
+        """evaluate.play_episodes(self.policy(depth, rule), n_boards, seed=seed, ...) through play and
+        play_ruled: the same dict, every value equal to the last bit except steps_run, which is a
+        multiple of chunk, plus mean_gain (the mean sum of merge rewards). The boards are played in
+        launches of `chunk` steps with one host check of done in between. Depths 1 and 2 go through
+        play (default chunk PLAY_CHUNK[depth]); depth 3 and a rule (17 depths 1..4 by the board's
+        blanks; `depth` is then not used) through play_ruled, depth 3 as the rule (3,) * 17, with
+        the default chunk ruled_chunk(the rule's largest depth, n_boards)."""
         if rule is None and depth not in (1, 2, 3):
             raise ValueError("play_episodes depth is 1, 2 or 3, got %r" % (depth,))
-        if rule is not None or depth == 3:
-            from .evaluate import play_episodes
-            return play_episodes(self.policy(depth, rule), n_boards, device=self.device, seed=seed, max_steps=max_steps,
-                                 return_scores=return_scores)
-        chunk = PLAY_CHUNK[depth] if chunk is None else int(chunk)
+        if rule is None and depth == 3:
+            rule = (3,) * 17
+        if rule is not None:
+            rule = _rule(rule)
+            default = ruled_chunk(max(rule), n_boards)
+        else:
+            default = PLAY_CHUNK[depth]
+        chunk = default if chunk is None else int(chunk)
         if chunk <= 0:
             raise ValueError("chunk must be positive, got %r" % (chunk,))
         env = VecGame(n_boards, device=self.device, seed=seed)
@@ -319,7 +370,10 @@ class NTupleNet:
         t = 0
         while t < max_steps:
             k = min(chunk, max_steps - t)
-            self.play(env, k, depth, length, gain, done)
+            if rule is not None:
+                self.play_ruled(env, k, rule, length, gain, done)
+            else:
+                self.play(env, k, depth, length, gain, done)
             t += k
             if bool((done != 0).all()):
                 break

@@ -84,6 +84,23 @@ tables (lines-squares 1,024 x 2,000 TD(0), 4x6 4,096 x 10,000 TC; --episodes eac
 up to --max-d4, default 3) with the evaluation seconds next to each, and policy(2), policy(3) and
 the rules on the learning test's recipe (lines-squares 1,024 x 1,000, 512 episodes, eval seed 1).
 Writes exp_ntuple_ruled.json.
+
+--play-ruled: whole games at a per-board depth in one launch (NTupleNet.play_ruled, r48_ntuple_play_ruled;
+play_episodes at depth 3 and under a rule). On the tables of the recorded recipes (lines-squares 1,024 x
+2,000 TD(0), 4x6 4,096 x 10,000 TC): (a) --episodes (default 4,096, eval seed 13) whole episodes under
+depth 3 and depth_rule(16, 1) (--long: depth_rule(16, 3) too) through play_episodes and through
+evaluate.play_episodes(net.policy(...)) -- the Python loop, which is what play_episodes was before -- in
+the same process, a first run of each and then the timed ones (two at depth 3, whose difference is the
+A/A spread; one under the rules), scores compared bit for bit and with the recorded ones; (b) the device
+time per step on 4,096 and 2^14 boards of running games, play_ruled's 20 steps in one launch against 20 x
+(search_ruled, env.step), alternated windows, for all-3 and depth_rule(16, 1); --ab-lib SO[,SO...]: other
+builds of the library (-DR48_NT_PLAY_RULED_WAVES=4 / 8 / 16) alternated in the same windows, boards
+compared bit for bit; (c) single launches at 4,096 boards from running games and from reset, and of
+play_episodes' chunk at 64 boards, the figures behind ntuple.RULED_BUDGET and RULED_MAX_CHUNK; the whole
+evaluations of (a) also with 64 and 512 episodes. Writes exp_ntuple_play_ruled.json. With --waves-ab, only the A/B of waves per
+board on whole evaluations: --episodes episodes to the end in play_episodes' chunks through each --ab-lib
+build, and single launches and whole evaluations of 64 boards, where one board's latency is what counts.
+Writes exp_ntuple_play_ruled_waves.json.
 """
 import argparse
 import json
@@ -1039,6 +1056,224 @@ def main_play(args):
         torch.cuda.empty_cache()
 
 
+def play_ruled_of_library(path, net):
+    """NTupleNet.play_ruled through r48_ntuple_play_ruled of another build of the library."""
+    import ctypes as C
+    from rein48_amd import _lib
+    f = C.CDLL(path).r48_ntuple_play_ruled
+    f.restype, f.argtypes = _lib.SIGNATURES["r48_ntuple_play_ruled"]
+
+    def play_ruled(env, n_steps, rule, length, gain, done):
+        step, reset = env.counters
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(f(_lib.ptr(env.boards), env.n, *net._lay(), _lib.ptr(net.tables), (C.c_uint8 * 17)(*rule), n_steps,
+                     env.seed, env.board_offset, step, _lib.ptr(length), _lib.ptr(gain), _lib.ptr(done), stream))
+        env.counters = ((step + n_steps) & 0xFFFFFFFF, reset)
+    return play_ruled
+
+
+def play_ruled_episode_times(net, name, rule, episodes, eval_seed, timed_runs):
+    """Whole episodes to the end: play_episodes (play_ruled in chunks) against evaluate.play_episodes (the
+    Python loop) on the same net in the same process: a first run of each, then timed_runs timed ones."""
+    from rein48_amd.ntuple import ruled_chunk
+    row = {"rule": name, "episodes": episodes, "eval_seed": eval_seed, "chunk": ruled_chunk(max(rule), episodes)}
+    if name == "depth3":                                      # as a caller asks for it: depth=3, the loop through search3
+        fused, policy = (lambda: net.play_episodes(episodes, seed=eval_seed, depth=3, return_scores=True)), net.policy(3)
+    else:
+        fused, policy = (lambda: net.play_episodes(episodes, seed=eval_seed, rule=rule, return_scores=True)), net.policy(rule=rule)
+    runs = {"play_episodes": fused,
+            "evaluate": lambda: play_episodes(policy, episodes, device=DEV, seed=eval_seed, return_scores=True)}
+    scores = {}
+    for which, fn in runs.items():
+        fn()
+        walls, devs = [], []
+        for _ in range(timed_runs):
+            ev, wall, dev_ms = timed(fn)
+            walls.append(wall)
+            devs.append(dev_ms)
+        scores[which] = ev.pop("scores")
+        ev.update(wall_seconds=walls[0], device_ms=devs[0], wall_seconds_runs=walls)
+        row[which] = ev
+    row["scores_bit_equal"] = bool(torch.equal(scores["play_episodes"], scores["evaluate"]))
+    row["wall_evaluate_over_play"] = row["evaluate"]["wall_seconds"] / row["play_episodes"]["wall_seconds"]
+    if timed_runs > 1:
+        row["a_a_spread"] = {k: max(row[k]["wall_seconds_runs"]) / min(row[k]["wall_seconds_runs"]) for k in runs}
+    return row
+
+
+def play_ruled_step_times(net, n, name, rule, k=20, ab_libs=()):
+    """Device time per step on n boards of running games: play_ruled's k steps in one launch against k x
+    (search_ruled, env.step), alternated windows; every call starts from the same boards and counter."""
+    start = running_boards(n)
+    env = VecGame(n, device=DEV, seed=7)
+    length, gain = (torch.zeros(n, dtype=torch.int32, device=DEV) for _ in range(2))
+    done = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    policy = net.policy(rule=rule)
+
+    def begin():
+        env.boards.copy_(start)
+        env.counters = (150, 0)
+
+    def fused():
+        begin()
+        net.play_ruled(env, k, rule, length, gain, done)
+
+    def composed():
+        begin()
+        for t in range(k):
+            env.step(policy(env.boards, t))
+    fns = {"play_ruled": fused, "composed": composed}
+    res = {"boards": n, "rule": name, "steps_per_call": k}
+    composed()
+    want = env.boards.clone()
+    fused()
+    res["play_equals_composed"] = bool(torch.equal(env.boards, want))
+    res["alive_after_the_call"] = float((done == 0).float().mean())
+    for path in ab_libs:
+        other = play_ruled_of_library(path, net)
+        tag = "play_ruled_" + os.path.splitext(os.path.basename(path))[0]
+
+        def fused_other(other=other):
+            begin()
+            other(env, k, rule, length, gain, done)
+        fused_other()
+        res[tag + "_equals_composed"] = bool(torch.equal(env.boards, want))
+        fns[tag] = fused_other
+    for which, t in alternated_ms(fns, warmup=2, windows=5, calls=3).items():
+        res[which] = {"us_per_step": t[0] / k * 1e3, "us_min": t[1] / k * 1e3, "us_max": t[2] / k * 1e3}
+    res["composed_over_play_ruled"] = res["composed"]["us_per_step"] / res["play_ruled"]["us_per_step"]
+    return res
+
+
+def play_ruled_launch_times(net, n, name, rule, chunks):
+    """The device time of single play_ruled launches of `chunk` steps at n boards: four consecutive
+    launches from boards of running games (few blanks: where depth 4 is) and four from reset."""
+    rows = []
+    for chunk in chunks:
+        row = {"boards": n, "rule": name, "chunk": chunk, "board_steps": n * chunk}
+        for begin in ("running", "reset"):
+            env = VecGame(n, device=DEV, seed=13)
+            env.reset()
+            if begin == "running":
+                env.boards.copy_(running_boards(n))
+                env.counters = (150, 0)
+            length, gain = (torch.zeros(n, dtype=torch.int32, device=DEV) for _ in range(2))
+            done = torch.zeros(n, dtype=torch.uint8, device=DEV)
+            ms = [timed(lambda: net.play_ruled(env, chunk, rule, length, gain, done))[2] for _ in range(4)]
+            row[begin] = {"longest_of_four_ms": max(ms), "launches_ms": ms,
+                          "alive_after_four": float((done == 0).float().mean())}
+        rows.append(row)
+    return rows
+
+
+def play_ruled_waves_ab(net, name, rule, episodes, eval_seed, ab_libs, small_n=64):
+    """The A/B of waves per board on what play_episodes does: whole episodes to the end in play_episodes'
+    chunks through each build's r48_ntuple_play_ruled (a first run, then the timed one), scores compared
+    bit for bit with the first build's; and single launches of play_episodes' chunk at small_n boards from
+    reset, where a launch costs its steps times one board's latency."""
+    from rein48_amd.ntuple import ruled_chunk
+    row = {"rule": name, "episodes": episodes, "eval_seed": eval_seed, "small_n": small_n, "builds": {}}
+    first = None
+    for path in ab_libs:
+        tag = os.path.splitext(os.path.basename(path))[0]
+        other = play_ruled_of_library(path, net)
+
+        def to_the_end(n=episodes, other=other):
+            chunk = ruled_chunk(max(rule), n)
+            env = VecGame(n, device=DEV, seed=eval_seed)
+            env.reset()
+            length, gain = (torch.zeros(n, dtype=torch.int32, device=DEV) for _ in range(2))
+            done = torch.zeros(n, dtype=torch.uint8, device=DEV)
+            for _ in range(0, 20000, chunk):
+                other(env, chunk, rule, length, gain, done)
+                if bool((done != 0).all()):
+                    break
+            return env.score().double().cpu()
+        to_the_end()
+        sc, wall, dev_ms = timed(to_the_end)
+        first = sc if first is None else first
+        res = {"wall_seconds": wall, "device_ms": dev_ms, "scores_equal_the_first_builds": bool(torch.equal(sc, first))}
+        chunk = ruled_chunk(max(rule), small_n)
+        env = VecGame(small_n, device=DEV, seed=eval_seed)
+        env.reset()
+        length, gain = (torch.zeros(small_n, dtype=torch.int32, device=DEV) for _ in range(2))
+        done = torch.zeros(small_n, dtype=torch.uint8, device=DEV)
+        ms = [timed(lambda: other(env, chunk, rule, length, gain, done))[2] for _ in range(4)]
+        res["small_n_launches"] = {"chunk": chunk, "launches_ms": ms, "alive_after_four": float((done == 0).float().mean()),
+                                   "mean_length": float(length.double().mean())}
+        _, res["small_n_whole_seconds"], _ = timed(lambda: to_the_end(small_n))
+        row["builds"][tag] = res
+    return row
+
+
+def main_play_ruled(args):
+    """--play-ruled [--ab-lib SO[,SO...]] [--max-d4 3]: play_ruled and play_episodes at depth 3 and under
+    rules against the Python loop of evaluate.play_episodes, on the tables of the recorded recipes."""
+    from rein48_amd.ntuple import ruled_chunk
+    ab_libs = [p for p in (args.ab_lib or "").split(",") if p]
+    out = {"device": torch.cuda.get_device_name(0), "ab_libs": ab_libs, "recipes": []}
+    recorded = {("lines-squares", "depth3"): 7135.3623046875, ("lines-squares", "3,d4<=1"): 7921.8720703125,
+                ("lines-squares", "3,d4<=3"): 8823.54345703125, ("4x6", "depth3"): 12457.6650390625,
+                ("4x6", "3,d4<=1"): 12909.06884765625, ("4x6", "3,d4<=3"): 13879.06494140625}
+
+    def save():
+        if args.out:
+            os.makedirs(args.out, exist_ok=True)
+            with open(os.path.join(args.out, "exp_ntuple_play_ruled%s.json" % ("_waves" if args.waves_ab else "")), "w") as f:
+                json.dump(out, f, indent=1)
+    rules = {"depth3": (3,) * 17, "3,d4<=1": NTupleNet.depth_rule(16, 1)}
+    if args.long:
+        rules["3,d4<=3"] = NTupleNet.depth_rule(16, 3)
+    for layout, n_boards, steps, alpha, tc in (("lines-squares", 1024, 2000, 0.25, False), ("4x6", 4096, 10000, 1.0, True)):
+        tr = NTupleTrainer(NTupleConfig(n_boards=n_boards, layout=layout, alpha=alpha, seed=0, tc=tc, fused=True), device=DEV)
+        tr.train_steps(steps)
+        torch.cuda.synchronize()
+        rec = {"layout": layout, "train_boards": n_boards, "train_steps": steps, "alpha": alpha, "tc": tc,
+               "episodes": [], "per_step": [], "launches": []}
+        out["recipes"].append(rec)
+        if args.waves_ab:                                     # the A/B of waves per board alone
+            for name, rule in rules.items():
+                r = play_ruled_waves_ab(tr.net, name, rule, args.episodes, 13, ab_libs)
+                rec["episodes"].append(r)
+                print(json.dumps(dict(r, layout=layout)), flush=True)
+                save()
+            del tr
+            torch.cuda.empty_cache()
+            continue
+        if not args.no_episodes:
+            for name, rule in rules.items():
+                r = play_ruled_episode_times(tr.net, name, rule, args.episodes, 13, 2 if name == "depth3" else 1)
+                if args.episodes == 4096:
+                    r["recorded_mean_score"] = recorded[(layout, name)]
+                    r["equals_the_recorded_score"] = r["play_episodes"]["mean_score"] == recorded[(layout, name)]
+                rec["episodes"].append(r)
+                print(json.dumps(dict(r, layout=layout)), flush=True)
+                save()
+        if not args.no_episodes:                              # few episodes: one board's latency is what counts
+            for episodes in (64, 512):
+                for name in ("depth3", "3,d4<=1"):
+                    r = play_ruled_episode_times(tr.net, name, rules[name], episodes, 13, 2)
+                    rec["episodes"].append(r)
+                    print(json.dumps(dict(r, layout=layout)), flush=True)
+            save()
+        for name in ("depth3", "3,d4<=1"):
+            for n in (int(s) for s in (args.sizes or "4096,16384").split(",")):
+                r = play_ruled_step_times(tr.net, n, name, rules[name], ab_libs=ab_libs)
+                rec["per_step"].append(r)
+                print(json.dumps(dict(r, layout=layout)), flush=True)
+            save()
+        for name, rule, chunks in (("all-1", (1,) * 17, (128, 256)), ("all-2", (2,) * 17, (32, 64)),
+                                   ("depth3", (3,) * 17, (8, 16, 32)), ("3,d4<=1", NTupleNet.depth_rule(16, 1), (2, 4)),
+                                   ("3,d4<=3", NTupleNet.depth_rule(16, 3), (1, 2, 4))):
+            for r in (play_ruled_launch_times(tr.net, 4096, name, rule, chunks) +
+                      play_ruled_launch_times(tr.net, 64, name, rule, (ruled_chunk(max(rule), 64),))):
+                rec["launches"].append(r)
+                print(json.dumps(dict(r, layout=layout)), flush=True)
+            save()
+        del tr
+        torch.cuda.empty_cache()
+
+
 def main_search(args):
     out = {"device": torch.cuda.get_device_name(0), "kernels": [], "scores": []}
     for layout in ("lines-squares", "4x6"):
@@ -1073,9 +1308,14 @@ def main():
     ap.add_argument("--ab-lib", default=None)
     ap.add_argument("--ruled", action="store_true")
     ap.add_argument("--max-d4", type=int, default=3)
+    ap.add_argument("--play-ruled", action="store_true")
+    ap.add_argument("--no-episodes", action="store_true")
+    ap.add_argument("--waves-ab", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("exp_ntuple.py needs a GPU")
+    if args.play_ruled:
+        return main_play_ruled(args)
     if args.ruled:
         return main_ruled(args)
     if args.play:
