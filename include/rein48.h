@@ -779,6 +779,68 @@ int r48_ntuple_apply_tc(const int8_t *boards, int64_t n, const uint8_t *valid, c
 int r48_ntuple_tc_rate(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
                        const float *tc_e, const float *tc_a, float *rate_out, void *stream);
 
+/* ---- Multi-stage tables with lazy weight promotion (Jaskowski 2016): the _staged twins.
+ * A staged network has n_cuts in 1..3 cuts (uint8, strictly ascending exponents in 1..15) and
+ * S = n_cuts + 1 stages; stage(b) = the number of cuts j with max over the cells of min(b[c], 15)
+ * >= cuts[j], of the board being EVALUATED (the afterstate, never the root of a search). tables,
+ * acc, cnt, tc_e and tc_a are [S][m][16^L], and hit (t, g) of board b is entry
+ * ((stage(b) * m + t) << 4L) + index. Each twin below is its plain entry point word for word with
+ * that entry -- the same order of summation, arithmetic, tie rule, outputs, checks and messages
+ * (under its own name) -- with `cuts, n_cuts` right after L.
+ * The four that update also take own, uint8 [S][m][16^L]: own[0] all 1 and every other entry 0
+ * before the first update. accumulate (and td_act) also set own[s][e] = 1 for every hit of a
+ * valid board with s >= 1. apply / apply_tc compute an entry's new value as the plain ones do,
+ * from tables[s][e] (and tc_e[s][e], tc_a[s][e]), and then copy it to tables[k][e] for k = s + 1,
+ * s + 2, ... while k < S and own[k][e] == 0: an entry that was never updated reads as the nearest
+ * lower owned stage's current value and its first update starts from there (tc_e / tc_a are not
+ * copied: that update runs at rate 1). After any sequence of updates tables[k][e] has the bits of
+ * tables[k - 1][e] wherever own[k][e] == 0. Bitwise reproducible and independent of the boards'
+ * order, as the plain update is.
+ * n_cuts == 0 is legal everywhere (cuts and own may then be NULL) and gives the bits of the plain
+ * entry point. R48_EINVAL (before any HIP call, after the plain entry point's own checks) for
+ * n_cuts outside 0..3, cuts NULL with n_cuts > 0, a cut outside 1..15, cuts not strictly ascending,
+ * and own NULL with n_cuts > 0. */
+int r48_ntuple_value_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                            const uint8_t *cuts, int32_t n_cuts, const float *tables, float *value, void *stream);
+int r48_ntuple_act_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                          const uint8_t *cuts, int32_t n_cuts, const float *tables, int8_t *actions, int8_t *after,
+                          float *value, int32_t *reward, uint8_t *legal, void *stream);
+int r48_ntuple_td_act_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                             const uint8_t *cuts, int32_t n_cuts, const float *tables, const int8_t *prev_after,
+                             const float *prev_value, const uint8_t *prev_done, const uint8_t *prev_valid,
+                             int8_t *actions, int8_t *after, float *value, int32_t *reward, uint8_t *legal,
+                             uint8_t *valid_out, float *delta_out, int64_t *acc, uint32_t *cnt, uint8_t *own,
+                             void *stream);
+int r48_ntuple_search_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                             const uint8_t *cuts, int32_t n_cuts, const float *tables, int32_t depth, int8_t *actions,
+                             float *q, uint8_t *legal, void *stream);
+int r48_ntuple_search3_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                              const uint8_t *cuts, int32_t n_cuts, const float *tables, int8_t *actions, float *q,
+                              uint8_t *legal, void *stream);
+int r48_ntuple_search_ruled_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                                   const uint8_t *cuts, int32_t n_cuts, const float *tables, const uint8_t *rule,
+                                   int8_t *actions, float *q, uint8_t *legal, uint8_t *depth_out, void *stream);
+int r48_ntuple_play_staged(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const uint8_t *cuts,
+                           int32_t n_cuts, const float *tables, int32_t depth, int32_t n_steps, uint64_t env_seed,
+                           int64_t gid0, uint32_t env_step, int32_t *length, int32_t *gain, uint8_t *done,
+                           void *stream);
+int r48_ntuple_play_ruled_staged(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                                 const uint8_t *cuts, int32_t n_cuts, const float *tables, const uint8_t *rule,
+                                 int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step, int32_t *length,
+                                 int32_t *gain, uint8_t *done, void *stream);
+int r48_ntuple_accumulate_staged(const int8_t *boards, int64_t n, const float *delta, const uint8_t *valid,
+                                 const uint8_t *cells, int32_t m, int32_t L, const uint8_t *cuts, int32_t n_cuts,
+                                 int64_t *acc, uint32_t *cnt, uint8_t *own, void *stream);
+int r48_ntuple_apply_staged(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
+                            int32_t L, const uint8_t *cuts, int32_t n_cuts, float step, float *tables, int64_t *acc,
+                            uint32_t *cnt, uint8_t *own, void *stream);
+int r48_ntuple_apply_tc_staged(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
+                               int32_t L, const uint8_t *cuts, int32_t n_cuts, float step, float *tables, float *tc_e,
+                               float *tc_a, int64_t *acc, uint32_t *cnt, uint8_t *own, void *stream);
+int r48_ntuple_tc_rate_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                              const uint8_t *cuts, int32_t n_cuts, const float *tc_e, const float *tc_a,
+                              float *rate_out, void *stream);
+
 /* Thread-local message of the last failed call on this thread ("" if none). */
 const char *r48_last_error(void);
 /* "rein48 <version> gfx950" */

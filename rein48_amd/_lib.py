@@ -145,6 +145,23 @@ SIGNATURES = {
     "r48_ntuple_apply": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P]),
     "r48_ntuple_apply_tc": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P, _P, _P]),
     "r48_ntuple_tc_rate": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _P]),
+    # the _staged twins: (cuts, n_cuts) right after L; the four that update end with own before the stream
+    "r48_ntuple_value_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _P]),
+    "r48_ntuple_act_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "r48_ntuple_td_act_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _P, _P, _P]),
+    "r48_ntuple_search_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _P, _P]),
+    "r48_ntuple_search3_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    "r48_ntuple_search_ruled_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "r48_ntuple_play_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _I32, _I32, _U64, _I64, _U32, _P, _P,
+                                         _P, _P]),
+    "r48_ntuple_play_ruled_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _I32, _U64, _I64, _U32, _P,
+                                               _P, _P, _P]),
+    "r48_ntuple_accumulate_staged": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
+    "r48_ntuple_apply_staged": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _P, _I32, C.c_float, _P, _P, _P, _P, _P]),
+    "r48_ntuple_apply_tc_staged": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _P, _I32, C.c_float, _P, _P, _P, _P, _P, _P,
+                                             _P]),
+    "r48_ntuple_tc_rate_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
     "r48_last_error": (C.c_char_p, []),
     "r48_version": (C.c_char_p, []),
 }

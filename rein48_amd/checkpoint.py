@@ -9,7 +9,7 @@ is bit-identical to training that never stopped (tests/test_checkpoint_gpu.py):
               Adam's m, v and step, the env's boards and counters, the env-step count, the update
               count, and the HBM replay ring (its counters and, unless replay=False, its contents in
               slot order: 38 B per stored transition)
-  NTupleTrainer  the tables (with cfg.tc also the error sums tc_e / tc_a), the env's boards and counters, the previous step's afterstates, values,
+  NTupleTrainer  the tables (with cfg.tc also the error sums tc_e / tc_a, with cfg.stages also the cuts and the own flags), the env's boards and counters, the previous step's afterstates, values,
               done and valid flags, and the step count (the update is deterministic: integer
               atomics, one plain table update per entry)
 Draws are keyed by counters, not by RNG state in memory, so restoring the
@@ -127,6 +127,8 @@ def save(trainer, path, replay=True):
                   prev_done=_cpu(trainer.prev_done), prev_valid=_cpu(trainer.prev_valid))
         if trainer.cfg.tc:
             st.update(tc_e=_cpu(trainer.net.tc_e), tc_a=_cpu(trainer.net.tc_a))
+        if trainer.net.cuts:
+            st.update(cfg=dict(cfg, stages=list(trainer.net.cuts)), stages=list(trainer.net.cuts), own=_cpu(trainer.net.own))
     elif kind == "a3c":
         st.update(net=_cpu_state(trainer.net), ms=_cpu(trainer.opt.ms), mom=_cpu(trainer.opt.mom),
                   env=_env_state(trainer.env), sample_ctr=int(trainer.sample_ctr))
@@ -169,10 +171,15 @@ def load(trainer, path):
             raise ValueError("checkpoint: %s = %r in the trainer, %r in %s" % (f, cfg[f], theirs, path))
     if kind == "ntuple" and st["cells"] != _cells(trainer.net):
         raise ValueError("checkpoint: layout cells %r in the trainer, %r in %s" % (_cells(trainer.net), st["cells"], path))
+    # the cuts of a staged net, compared as cuts like the cells; a file without the key is an unstaged trainer's
+    if kind == "ntuple" and tuple(st.get("stages", ())) != trainer.net.cuts:
+        raise ValueError("checkpoint: stages %r in the trainer, %r in %s" % (trainer.net.cuts, tuple(st.get("stages", ())), path))
     dev = trainer.device
     with torch.no_grad():
         if kind == "ntuple":
             trainer.net.tables.copy_(st["tables"].to(dev))
+            if trainer.net.cuts:
+                trainer.net.own.copy_(st["own"].to(dev))
             if trainer.cfg.tc:
                 trainer.net.tc_e.copy_(st["tc_e"].to(dev))
                 trainer.net.tc_a.copy_(st["tc_a"].to(dev))

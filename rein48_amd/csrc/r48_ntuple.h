@@ -61,8 +61,46 @@
 // on n, on how the children were dealt or on which wave did what -- nor on the rule's other
 // entries. A roomy board at depth 4 costs about a hundred times depth 3: the rule is the cost
 // guard.
+//
+// Stages (multi-stage tables with lazy weight promotion; Jaskowski 2016). A staged net has n_cuts in
+// 1..3 CUTS, strictly ascending exponents in 1..15, and S = n_cuts + 1 stages:
+//     stage(b) = #{ j : max over the 16 cells of min(b[c], 15) >= cuts[j] }
+// of the board being EVALUATED -- the afterstate, never the root of a search or the env board.
+// tables, acc, cnt and with TC tc_e / tc_a are [S][m][16^L]; own is uint8 [S][m][16^L] with own[0]
+// all 1 and every other entry 0 at the start; everything else starts at zero. Hit p = 8t + g of
+// board b reads entry
+//     ((stage(b) * m + t) << 4L) + index(b, placed[p]).
+// Everything read-only (V, act, every search depth, the ruled search, both play kernels, tc_rate) is
+// the contract above word for word with that entry: the same summation order, the same nt_fma /
+// butterfly / nt_q2 arithmetic, the same first maximiser, and still nothing depends on the batch
+// position, on n or on which wave did what. A reader never follows a fallback chain.
+// The update (accumulate then apply, or td_act then apply):
+//   1. MARK, in the accumulate walk (nt_add_hits, so in k_nt_td_act too): every hit (s, e) of a
+//      valid board with s >= 1 sets own[s][e] = 1, a plain byte store of one value, complete before
+//      apply's launch begins.
+//   2. APPLY: the lane that owns touched entry (s, e) (it got the count from the exchange) computes
+//      the new value exactly as the unstaged update does, from tables[s][e] (TC: tc_e[s][e] and
+//      tc_a[s][e] by nt_tc_update), stores it and then PUSHES it: for k = s + 1, s + 2, ... while
+//      k < S and own[k][e] == 0, tables[k][e] = new; it stops at the first owned stage. tc_e and tc_a
+//      are never pushed: an entry's first update in a new stage runs at rate 1.
+// This is lazy weight promotion: the first update of (s, e) starts from the value the nearest lower
+// owned stage had after the previous update call, and until then (s, e) reads as that stage's
+// current value. A call's marks are all set before any of its exchanges, so the owner of (0, e)
+// never writes into a stage that the same call takes ownership of: no race, no dependence on the
+// order of the boards, bitwise reproducible as the unstaged update is.
+// Invariant: after any sequence of updates, for every k >= 1 and e with own[k][e] == 0, tables[k][e]
+// has the bits of tables[k - 1][e].
+// Staging is a compile-time parameter of every body below: the policy NtPlain (no stages, the
+// entry offset is the constant 0 and nothing is computed) or NtCuts (the cuts in one word).
+// nt_staged_update_pull restates the update on the host in the PULL form: an unowned entry is not
+// stored at all, a read resolves to the nearest lower owned stage and a first touch copies it.
 #pragma once
 #include <stdint.h>
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+#include <map>
+#include <vector>
+#endif
 
 #include "r48_board.h"
 
@@ -147,6 +185,75 @@ R48_HD NtBoard nt_pack(const Board &b)
     return NtBoard{nt_pack_row(b.w0) | (nt_pack_row(b.w1) << 16), nt_pack_row(b.w2) | (nt_pack_row(b.w3) << 16)};
 }
 
+#if defined(__HIPCC__)
+#define R48_NO_UNROLL _Pragma("unroll 1")
+#else
+#define R48_NO_UNROLL
+#endif
+
+// ---- stages -----------------------------------------------------------------------------------
+static constexpr int kNtMaxCuts = 3;
+
+// the two staging policies: none, or the checked cuts in one word (cut j in byte j, n of them)
+struct NtPlain {};
+struct NtCuts {
+    uint32_t w;
+    int32_t n;
+};
+
+// NULL, or what is wrong with the cuts of a staged entry point (n_cuts == 0: unstaged, cuts unused)
+inline const char *nt_cuts_check(const uint8_t *cuts, int n_cuts)
+{
+    if (n_cuts < 0 || n_cuts > kNtMaxCuts)
+        return "n_cuts must be 0..3";
+    if (n_cuts > 0 && !cuts)
+        return "cuts is NULL";
+    for (int j = 0; j < n_cuts; j++) {
+        if (cuts[j] < 1 || cuts[j] > 15)
+            return "a cut is not in 1..15";
+        if (j > 0 && cuts[j] <= cuts[j - 1])
+            return "cuts are not strictly ascending";
+    }
+    return nullptr;
+}
+
+inline NtCuts nt_cuts_pack(const uint8_t *cuts, int n_cuts)
+{
+    NtCuts c{0u, n_cuts};
+    for (int j = 0; j < n_cuts; j++)
+        c.w |= (uint32_t)cuts[j] << (8 * j);
+    return c;
+}
+
+// stage(b) of the contract, from the row words (bytes <= 0x7F): byte + (0x80 - cut) has bit 7 set
+// exactly where the byte is >= cut, and a byte of 16..18 is above every cut as its clamp 15 is. Per
+// cut four adds, two ors, one and, a compare and an add; the addend is wave-uniform.
+R48_HD uint32_t nt_stage(const NtCuts &c, const Board &b)
+{
+    uint32_t s = 0u;
+    R48_NO_UNROLL
+    for (int j = 0; j < c.n; j++) {
+        const uint32_t k = (0x80u - ((c.w >> (8 * j)) & 0xFFu)) * 0x01010101u;
+        const uint32_t hit = or3(b.w0 + k, b.w1 + k, b.w2 + k) | (b.w3 + k);
+        s += (hit & 0x80808080u) != 0u ? 1u : 0u;
+    }
+    return s;
+}
+
+// the offset of the board's stage in the contiguous [S][m][16^L] arrays: (stage * m) << 4L, below
+// 2^29. Without stages the constant 0.
+template <int L>
+R48_HD uint32_t nt_base(const NtPlain &, int32_t, const Board &)
+{
+    return 0u;
+}
+
+template <int L>
+R48_HD uint32_t nt_base(const NtCuts &c, int32_t m, const Board &b)
+{
+    return (nt_stage(c, b) * (uint32_t)m) << (4 * L);
+}
+
 // entry index of one placed tuple
 template <int L>
 R48_HD uint32_t nt_index(const NtBoard &b, uint64_t placed)
@@ -161,16 +268,17 @@ R48_HD uint32_t nt_index(const NtBoard &b, uint64_t placed)
     return idx;
 }
 
-// entry of hit p = 8t + g in the contiguous tables[m][16^L]
+// entry of hit p = 8t + g in the contiguous tables[m][16^L]; staged: in [S][m][16^L], base =
+// nt_base of the board
 template <int L>
-R48_HD uint32_t nt_entry(const NtBoard &b, const NtLayout &lay, int p)
+R48_HD uint32_t nt_entry(const NtBoard &b, const NtLayout &lay, int p, uint32_t base = 0u)
 {
-    return ((uint32_t)(p >> 3) << (4 * L)) + nt_index<L>(b, lay.placed[p]);
+    return base + ((uint32_t)(p >> 3) << (4 * L)) + nt_index<L>(b, lay.placed[p]);
 }
 
 // V(b) in the contract's order. The loads of two tuples (16 hits) are issued before their adds.
 template <int L>
-R48_HD float nt_value(const NtBoard &b, const NtLayout &lay, const float *__restrict__ tables)
+R48_HD float nt_value(const NtBoard &b, const NtLayout &lay, const float *__restrict__ tables, uint32_t base = 0u)
 {
     const int np = kNtSyms * lay.m;
     float sum = 0.0f;
@@ -179,7 +287,7 @@ R48_HD float nt_value(const NtBoard &b, const NtLayout &lay, const float *__rest
         float v[16];
         R48_UNROLL
         for (int j = 0; j < 16; j++)
-            v[j] = tables[nt_entry<L>(b, lay, p + j)];
+            v[j] = tables[nt_entry<L>(b, lay, p + j, base)];
         R48_UNROLL
         for (int j = 0; j < 16; j++)
             sum += v[j];
@@ -188,7 +296,7 @@ R48_HD float nt_value(const NtBoard &b, const NtLayout &lay, const float *__rest
         float v[8];
         R48_UNROLL
         for (int j = 0; j < 8; j++)
-            v[j] = tables[nt_entry<L>(b, lay, p + j)];
+            v[j] = tables[nt_entry<L>(b, lay, p + j, base)];
         R48_UNROLL
         for (int j = 0; j < 8; j++)
             sum += v[j];
@@ -258,7 +366,7 @@ R48_HD long long nt_fixed_delta(float delta)
 // 8 of A) are issued before their rates are formed.
 template <int L>
 R48_HD float nt_tc_rate_mean(const NtBoard &b, const NtLayout &lay, const float *__restrict__ tc_e,
-                             const float *__restrict__ tc_a)
+                             const float *__restrict__ tc_a, uint32_t base = 0u)
 {
     const int np = kNtSyms * lay.m;
     float sum = 0.0f;
@@ -266,7 +374,7 @@ R48_HD float nt_tc_rate_mean(const NtBoard &b, const NtLayout &lay, const float 
         float e[kNtSyms], a[kNtSyms];
         R48_UNROLL
         for (int j = 0; j < kNtSyms; j++) {
-            const uint32_t at = nt_entry<L>(b, lay, p + j);
+            const uint32_t at = nt_entry<L>(b, lay, p + j, base);
             e[j] = tc_e[at];
             a[j] = tc_a[at];
         }
@@ -278,12 +386,6 @@ R48_HD float nt_tc_rate_mean(const NtBoard &b, const NtLayout &lay, const float 
 }
 
 // ---- the search -------------------------------------------------------------------------------
-
-#if defined(__HIPCC__)
-#define R48_NO_UNROLL _Pragma("unroll 1")
-#else
-#define R48_NO_UNROLL
-#endif
 
 R48_HD float nt_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
@@ -318,16 +420,18 @@ R48_HD uint32_t nt_cell(const Board &b, uint32_t c)
     return (w >> (8u * (c & 3u))) & 0xFFu;
 }
 
-// (float)reward + V(afterstate): the score of one move, at either depth
-template <int L>
-R48_HD float nt_score(const Board &after, uint32_t reward, const NtLayout &lay, const float *__restrict__ tables)
+// (float)reward + V(afterstate): the score of one move, at either depth. The stage is the
+// afterstate's.
+template <int L, class Stg = NtPlain>
+R48_HD float nt_score(const Board &after, uint32_t reward, const NtLayout &lay, const float *__restrict__ tables,
+                      const Stg &stg = Stg())
 {
-    return (float)(int32_t)reward + nt_value<L>(nt_pack(after), lay, tables);
+    return (float)(int32_t)reward + nt_value<L>(nt_pack(after), lay, tables, nt_base<L>(stg, lay.m, after));
 }
 
 // the best score over the legal moves of `child` (act's), 0 where it has none
-template <int L>
-R48_HD float nt_leaf(const Board &child, const NtLayout &lay, const float *__restrict__ tables)
+template <int L, class Stg = NtPlain>
+R48_HD float nt_leaf(const Board &child, const NtLayout &lay, const float *__restrict__ tables, const Stg &stg = Stg())
 {
     const Moves4 m = move_rows4<true>(child);
     const uint32_t lg = nt_legal4(m, child);
@@ -337,7 +441,7 @@ R48_HD float nt_leaf(const Board &child, const NtLayout &lay, const float *__res
     for (uint32_t a = 0; a < 4u; a++) {
         if (!((lg >> a) & 1u))
             continue;
-        const float s = nt_score<L>(nt_pick(m, a), nt_pick_reward(m, a), lay, tables);
+        const float s = nt_score<L>(nt_pick(m, a), nt_pick_reward(m, a), lay, tables, stg);
         if (!have || s > best) {
             have = true;
             best = s;
@@ -425,15 +529,16 @@ inline float nt_sum16(const float *x)
     return v[0];
 }
 
-template <int L>
-inline float nt_q_level(const Board &s, uint32_t r, const NtLayout &lay, const float *tables, int k);
+template <int L, class Stg = NtPlain>
+inline float nt_q_level(const Board &s, uint32_t r, const NtLayout &lay, const float *tables, int k,
+                        const Stg &stg = Stg());
 
 // best_k(board) of the contract, on the host: plain recursion. best_1 is nt_leaf.
-template <int L>
-inline float nt_best(const Board &board, const NtLayout &lay, const float *tables, int k)
+template <int L, class Stg = NtPlain>
+inline float nt_best(const Board &board, const NtLayout &lay, const float *tables, int k, const Stg &stg = Stg())
 {
     if (k <= 1)
-        return nt_leaf<L>(board, lay, tables);
+        return nt_leaf<L>(board, lay, tables, stg);
     const Moves4 m = move_rows4<true>(board);
     const uint32_t lg = nt_legal4(m, board);
     float best = 0.0f;
@@ -441,7 +546,7 @@ inline float nt_best(const Board &board, const NtLayout &lay, const float *table
     for (uint32_t a = 0; a < 4u; a++) {
         if (!((lg >> a) & 1u))
             continue;
-        const float s = nt_q_level<L>(nt_pick(m, a), nt_pick_reward(m, a), lay, tables, k);
+        const float s = nt_q_level<L>(nt_pick(m, a), nt_pick_reward(m, a), lay, tables, k, stg);
         if (!have || s > best) {
             have = true;
             best = s;
@@ -451,8 +556,8 @@ inline float nt_best(const Board &board, const NtLayout &lay, const float *table
 }
 
 // Q_k(a), k >= 2, from the move's afterstate s and reward r
-template <int L>
-inline float nt_q_level(const Board &s, uint32_t r, const NtLayout &lay, const float *tables, int k)
+template <int L, class Stg>
+inline float nt_q_level(const Board &s, uint32_t r, const NtLayout &lay, const float *tables, int k, const Stg &stg)
 {
     float x[16];
     for (uint32_t c = 0; c < 16u; c++) {
@@ -462,7 +567,7 @@ inline float nt_q_level(const Board &s, uint32_t r, const NtLayout &lay, const f
         Board two = s, four = s;
         place(two, c, 1u, true);
         place(four, c, 2u, true);
-        x[c] = nt_fma(9.0f, nt_best<L>(two, lay, tables, k - 1), nt_best<L>(four, lay, tables, k - 1));
+        x[c] = nt_fma(9.0f, nt_best<L>(two, lay, tables, k - 1, stg), nt_best<L>(four, lay, tables, k - 1, stg));
     }
     return nt_q2(r, nt_sum16(x), blanks(s).n);
 }
@@ -471,9 +576,9 @@ inline float nt_q_level(const Board &s, uint32_t r, const NtLayout &lay, const f
 // k_nt_search3 and k_nt_search_ruled, which run the same nt_leaf / nt_fma / nt_q2 / nt_argmax4 but
 // spread the children over lanes and waves and sum with the butterfly. Returns the action; q[4]
 // and legal as the kernels write them.
-template <int L>
+template <int L, class Stg = NtPlain>
 inline uint32_t nt_search_board(const Board &b, const NtLayout &lay, const float *tables, int depth, float q[4],
-                                uint32_t &legal)
+                                uint32_t &legal, const Stg &stg = Stg())
 {
     const Moves4 m = move_rows4<true>(b);
     legal = nt_legal4(m, b);
@@ -484,10 +589,10 @@ inline uint32_t nt_search_board(const Board &b, const NtLayout &lay, const float
         const Board s = nt_pick(m, a);
         const uint32_t r = nt_pick_reward(m, a);
         if (depth == 1) {
-            q[a] = nt_score<L>(s, r, lay, tables);
+            q[a] = nt_score<L>(s, r, lay, tables, stg);
             continue;
         }
-        q[a] = nt_q_level<L>(s, r, lay, tables, depth);
+        q[a] = nt_q_level<L>(s, r, lay, tables, depth, stg);
     }
     return nt_argmax4(q[0], q[1], q[2], q[3]);
 }
@@ -526,14 +631,14 @@ inline uint32_t nt_rule_depth(const uint8_t *rule, const Board &b) { return rule
 
 // The ruled contract for one board: nt_search_board at rule[blanks]; depth_out (nullable) as the
 // kernel writes it, whether or not the board has a legal move.
-template <int L>
+template <int L, class Stg = NtPlain>
 inline uint32_t nt_search_board_ruled(const Board &b, const NtLayout &lay, const float *tables, const uint8_t *rule,
-                                      float q[4], uint32_t &legal, uint8_t *depth_out)
+                                      float q[4], uint32_t &legal, uint8_t *depth_out, const Stg &stg = Stg())
 {
     const uint32_t d = nt_rule_depth(rule, b);
     if (depth_out)
         *depth_out = (uint8_t)d;
-    return nt_search_board<L>(b, lay, tables, (int)d, q, legal);
+    return nt_search_board<L>(b, lay, tables, (int)d, q, legal, stg);
 }
 
 // ---- playing whole games ----------------------------------------------------------------------
@@ -563,14 +668,15 @@ R48_HD uint32_t nt_play_done(const Board &b) { return game_over(b, blanks(b).n) 
 // The contract for one board, serially: n_steps x (nt_search_board, nt_play_step), every step made
 // whether the board is finished or not. length and gain are added to, done is written (each
 // nullable); n_steps == 0 touches nothing.
-template <int L>
+template <int L, class Stg = NtPlain>
 inline void nt_play_board(Board &board, const NtLayout &lay, const float *tables, int depth, int n_steps, uint32_t k0,
-                          uint32_t k1, uint64_t gid, uint32_t step0, int32_t *length, int32_t *gain, uint8_t *done)
+                          uint32_t k1, uint64_t gid, uint32_t step0, int32_t *length, int32_t *gain, uint8_t *done,
+                          const Stg &stg = Stg())
 {
     for (int t = 0; t < n_steps; t++) {
         float q[4];
         uint32_t legal;
-        const uint32_t action = nt_search_board<L>(board, lay, tables, depth, q, legal);
+        const uint32_t action = nt_search_board<L>(board, lay, tables, depth, q, legal, stg);
         const StepOut o = nt_play_step(board, action, gid, step0 + (uint32_t)t, k0, k1);
         if (length)
             *length += (int32_t)o.changed;
@@ -592,15 +698,15 @@ inline void nt_play_board(Board &board, const NtLayout &lay, const float *tables
 // every later step is the identity on it, whatever its depth. Everything equals n_steps x
 // (r48_ntuple_search_ruled, r48_env_step) bit for bit, for every n, gid, step0 and rule; the bits
 // depend neither on the number of waves that share a board nor on how its children were dealt.
-template <int L>
+template <int L, class Stg = NtPlain>
 inline void nt_play_board_ruled(Board &board, const NtLayout &lay, const float *tables, const uint8_t *rule, int n_steps,
                                 uint32_t k0, uint32_t k1, uint64_t gid, uint32_t step0, int32_t *length, int32_t *gain,
-                                uint8_t *done)
+                                uint8_t *done, const Stg &stg = Stg())
 {
     for (int t = 0; t < n_steps; t++) {
         float q[4];
         uint32_t legal;
-        const uint32_t action = nt_search_board_ruled<L>(board, lay, tables, rule, q, legal, nullptr);
+        const uint32_t action = nt_search_board_ruled<L>(board, lay, tables, rule, q, legal, nullptr, stg);
         const StepOut o = nt_play_step(board, action, gid, step0 + (uint32_t)t, k0, k1);
         if (length)
             *length += (int32_t)o.changed;
@@ -610,5 +716,65 @@ inline void nt_play_board_ruled(Board &board, const NtLayout &lay, const float *
             *done = (uint8_t)o.done;
     }
 }
+
+// ---- the staged update on the host, in the PULL form -------------------------------------------
+// The kernels store an unowned entry's value eagerly (the owner of the nearest lower owned stage
+// pushes it). Here nothing is pushed: tables[k][e] of an unowned (k, e) is never read or written, a
+// read RESOLVES to the nearest lower owned stage (stage 0 owns everything), and the first touch of
+// (s, e) copies the resolved value in before the call's updates run. The contract says the two
+// agree bit for bit on every resolved entry.
+#if !defined(__HIP_DEVICE_COMPILE__)
+
+// the value entry e (an offset within one stage, t * 16^L + index) reads as in stage s
+inline float nt_pull_read(const float *tables, const uint8_t *own, int64_t stage_size, int s, int64_t e)
+{
+    while (s > 0 && !own[s * stage_size + e])
+        s--;
+    return tables[s * stage_size + e];
+}
+
+// One update call, serially: boards[i] with valid[i] != 0 (valid nullable) add delta[i] over their 8m
+// hits; every touched entry then moves by step * its mean delta, with tc_e / tc_a (both or neither)
+// by nt_tc_update. All arrays [S][m][16^L], S = cuts.n + 1.
+template <int L>
+inline void nt_staged_update_pull(const Board *boards, const float *delta, const uint8_t *valid, int64_t n,
+                                  const NtLayout &lay, const NtCuts &cuts, float step, float *tables, float *tc_e,
+                                  float *tc_a, uint8_t *own)
+{
+    struct Sum {
+        long long acc = 0;
+        uint32_t cnt = 0;
+    };
+    const int64_t stage_size = (int64_t)lay.m << (4 * L);
+    std::map<int64_t, Sum> sums;   // by s * stage_size + e: ascending stages for one e
+    for (int64_t i = 0; i < n; i++) {
+        if (valid && !valid[i])
+            continue;
+        const NtBoard nb = nt_pack(boards[i]);
+        const int64_t s = nt_stage(cuts, boards[i]);
+        for (int p = 0; p < kNtSyms * lay.m; p++) {
+            Sum &x = sums[s * stage_size + nt_entry<L>(nb, lay, p)];
+            x.acc += nt_fixed_delta(delta[i]);
+            x.cnt += 1u;
+        }
+    }
+    // first touches: the pre-call value of the nearest lower owned stage (ascending keys, so a lower
+    // stage touched for the first time in this call is resolved before a higher one copies from it)
+    for (const auto &kv : sums) {
+        const int64_t s = kv.first / stage_size, e = kv.first % stage_size;
+        if (!own[kv.first]) {
+            tables[kv.first] = nt_pull_read(tables, own, stage_size, (int)s, e);
+            own[kv.first] = 1;
+        }
+    }
+    for (const auto &kv : sums) {
+        const float mean = nt_mean(kv.second.acc, kv.second.cnt);
+        if (tc_e)
+            nt_tc_update(tables[kv.first], tc_e[kv.first], tc_a[kv.first], mean, step);
+        else
+            tables[kv.first] += step * mean;
+    }
+}
+#endif
 
 }  // namespace r48

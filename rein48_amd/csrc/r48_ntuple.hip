@@ -70,15 +70,31 @@ int launched(const char *what)
 
 bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
-template <int L>
+// Staging (r48_ntuple.h) is a compile-time parameter of every kernel: a trailing parameter pack C
+// that is empty for the unstaged kernel -- its arguments are then exactly what they were -- and one
+// argument for the staged twin: the cuts (r48::NtCuts) for a kernel that only reads, the cuts and
+// the own flags (NtCutsOwn) for one that updates. nt_stg(cuts...) is the policy the bodies take.
+struct NtCutsOwn {
+    r48::NtCuts cuts;
+    uint8_t *own;
+};
+
+__device__ __forceinline__ r48::NtPlain nt_stg() { return r48::NtPlain{}; }
+__device__ __forceinline__ r48::NtCuts nt_stg(const r48::NtCuts &c) { return c; }
+__device__ __forceinline__ r48::NtCuts nt_stg(const NtCutsOwn &c) { return c.cuts; }
+__device__ __forceinline__ uint8_t *nt_own() { return nullptr; }
+__device__ __forceinline__ uint8_t *nt_own(const NtCutsOwn &c) { return c.own; }
+
+template <int L, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_value(const int8_t *__restrict__ boards, int64_t n,
                                                      const r48::NtLayout lay, const float *__restrict__ tables,
-                                                     float *__restrict__ value)
+                                                     float *__restrict__ value, const C... cuts)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
         return;
-    value[i] = r48::nt_value<L>(r48::nt_pack(r48::load_board(boards, i)), lay, tables);
+    const r48::Board b = r48::load_board(boards, i);
+    value[i] = r48::nt_value<L>(r48::nt_pack(b), lay, tables, r48::nt_base<L>(nt_stg(cuts...), lay.m, b));
 }
 
 // the move the one-ply search chooses
@@ -91,9 +107,9 @@ struct NtMove {
 // The one-ply search of one board in one lane: the four moves in registers (move_rows4), V of the
 // legal ones only, the first maximiser of reward + V. No legal move: action 0, the board itself,
 // value 0, reward 0.
-template <int L>
+template <int L, class Stg>
 __device__ __forceinline__ NtMove nt_act_board(const r48::Board &b, const r48::NtLayout &lay,
-                                               const float *__restrict__ tables)
+                                               const float *__restrict__ tables, const Stg &stg)
 {
     const r48::Moves4 m = r48::move_rows4<true>(b);
     const uint32_t lg = r48::nt_legal4(m, b);
@@ -108,7 +124,7 @@ __device__ __forceinline__ NtMove nt_act_board(const r48::Board &b, const r48::N
         // a is uniform: scalar-conditioned selects, no indexed private array
         const r48::Board c = a == 0u ? m.up : a == 1u ? m.down : a == 2u ? m.left : m.right;
         const uint32_t r = a == 0u ? m.r_up : a == 1u ? m.r_down : a == 2u ? m.r_left : m.r_right;
-        const float v = r48::nt_value<L>(r48::nt_pack(c), lay, tables);
+        const float v = r48::nt_value<L>(r48::nt_pack(c), lay, tables, r48::nt_base<L>(stg, lay.m, c));
         const float s = (float)(int32_t)r + v;
         if (!have || s > best_s) {
             have = true;
@@ -122,17 +138,17 @@ __device__ __forceinline__ NtMove nt_act_board(const r48::Board &b, const r48::N
     return NtMove{best_b, best_v, best_r, best_a, lg};
 }
 
-template <int L>
+template <int L, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_act(const int8_t *__restrict__ boards, int64_t n,
                                                    const r48::NtLayout lay, const float *__restrict__ tables,
                                                    int8_t *__restrict__ actions, int8_t *__restrict__ after,
                                                    float *__restrict__ value, int32_t *__restrict__ reward,
-                                                   uint8_t *__restrict__ legal)
+                                                   uint8_t *__restrict__ legal, const C... cuts)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
         return;
-    const NtMove mv = nt_act_board<L>(r48::load_board(boards, i), lay, tables);
+    const NtMove mv = nt_act_board<L>(r48::load_board(boards, i), lay, tables, nt_stg(cuts...));
     actions[i] = (int8_t)mv.action;
     if (after)
         *reinterpret_cast<uint4 *>(after + 16 * i) = make_uint4(mv.after.w0, mv.after.w1, mv.after.w2, mv.after.w3);
@@ -146,17 +162,25 @@ __global__ __launch_bounds__(kBlock) void k_nt_act(const int8_t *__restrict__ bo
 
 // The accumulate half of the update for one board: every hit (t, g) adds 1 to cnt[e] and delta in
 // fixed point to acc[e]. Integer atomics, so the sums do not depend on the order of the lanes.
-template <int L>
+// MARK (a staged update; base = nt_base of the board): a board above stage 0 also sets own[e] = 1
+// for each of its hits -- the update's mark, a plain byte store of the one value every marker
+// writes, finished with this launch and so before apply's begins.
+template <int L, bool MARK = false>
 __device__ __forceinline__ void nt_add_hits(const r48::NtBoard &b, const r48::NtLayout &lay, float delta,
-                                            unsigned long long *__restrict__ acc, uint32_t *__restrict__ cnt)
+                                            unsigned long long *__restrict__ acc, uint32_t *__restrict__ cnt,
+                                            uint32_t base = 0u, uint8_t *__restrict__ own = nullptr)
 {
     const unsigned long long q = (unsigned long long)r48::nt_fixed_delta(delta);   // two's complement: wraps as int64 adds
     for (int t = 0; t < lay.m; t++) {
 #pragma unroll
         for (int g = 0; g < r48::kNtSyms; g++) {
-            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g);
+            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g, base);
             atomicAdd(&cnt[e], 1u);
             atomicAdd(&acc[e], q);
+            if constexpr (MARK) {
+                if (base != 0u)
+                    own[e] = 1;
+            }
         }
     }
 }
@@ -175,13 +199,13 @@ __device__ __forceinline__ void nt_add_hits(const r48::NtBoard &b, const r48::Nt
 // depend on their order, so the launch computes what act, the torch expression for delta and
 // accumulate compute one after another, bit for bit. after / value / valid_out must not be the
 // prev_ buffers (the entry point refuses it): apply reads the old ones after this kernel.
-template <int L>
+template <int L, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_td_act(
     const int8_t *__restrict__ boards, int64_t n, const r48::NtLayout lay, const float *__restrict__ tables,
     const int8_t *__restrict__ prev_after, const float *__restrict__ prev_value, const uint8_t *__restrict__ prev_done,
     const uint8_t *__restrict__ prev_valid, int8_t *__restrict__ actions, int8_t *__restrict__ after,
     float *__restrict__ value, int32_t *__restrict__ reward, uint8_t *__restrict__ legal, uint8_t *__restrict__ valid_out,
-    float *__restrict__ delta_out, unsigned long long *__restrict__ acc, uint32_t *__restrict__ cnt)
+    float *__restrict__ delta_out, unsigned long long *__restrict__ acc, uint32_t *__restrict__ cnt, const C... cuts)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
@@ -190,7 +214,7 @@ __global__ __launch_bounds__(kBlock) void k_nt_td_act(
     const r48::Board pb = r48::load_board(prev_after, i);
     const float pv = prev_value[i];
     const uint32_t pd = prev_done[i], pok = prev_valid[i];
-    const NtMove mv = nt_act_board<L>(b, lay, tables);
+    const NtMove mv = nt_act_board<L>(b, lay, tables, nt_stg(cuts...));
     actions[i] = (int8_t)mv.action;
     *reinterpret_cast<uint4 *>(after + 16 * i) = make_uint4(mv.after.w0, mv.after.w1, mv.after.w2, mv.after.w3);
     value[i] = mv.value;
@@ -202,20 +226,23 @@ __global__ __launch_bounds__(kBlock) void k_nt_td_act(
     if (delta_out)
         delta_out[i] = delta;
     if (pok)
-        nt_add_hits<L>(r48::nt_pack(pb), lay, delta, acc, cnt);
+        nt_add_hits<L, sizeof...(C) != 0>(r48::nt_pack(pb), lay, delta, acc, cnt,
+                                          r48::nt_base<L>(nt_stg(cuts...), lay.m, pb), nt_own(cuts...));
 }
 
-template <int L>
+template <int L, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_accumulate(const int8_t *__restrict__ boards, int64_t n,
                                                           const float *__restrict__ delta,
                                                           const uint8_t *__restrict__ valid, const r48::NtLayout lay,
                                                           unsigned long long *__restrict__ acc,
-                                                          uint32_t *__restrict__ cnt)
+                                                          uint32_t *__restrict__ cnt, const C... cuts)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n || (valid && !valid[i]))
         return;
-    nt_add_hits<L>(r48::nt_pack(r48::load_board(boards, i)), lay, delta[i], acc, cnt);
+    const r48::Board b = r48::load_board(boards, i);
+    nt_add_hits<L, sizeof...(C) != 0>(r48::nt_pack(b), lay, delta[i], acc, cnt,
+                                      r48::nt_base<L>(nt_stg(cuts...), lay.m, b), nt_own(cuts...));
 }
 
 // The apply half: every hit again. The one lane of the launch whose exchange takes an entry's
@@ -223,12 +250,12 @@ __global__ __launch_bounds__(kBlock) void k_nt_accumulate(const int8_t *__restri
 // entry's sum with nt_take_sum. Both scratch words are zero afterwards.
 template <int L, class Update>
 __device__ __forceinline__ void nt_owned_hits(const r48::NtBoard &b, const r48::NtLayout &lay,
-                                              uint32_t *__restrict__ cnt, Update update)
+                                              uint32_t *__restrict__ cnt, Update update, uint32_t base = 0u)
 {
     for (int t = 0; t < lay.m; t++) {
 #pragma unroll
         for (int g = 0; g < r48::kNtSyms; g++) {
-            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g);
+            const uint32_t e = r48::nt_entry<L>(b, lay, r48::kNtSyms * t + g, base);
             const uint32_t c = atomicExch(&cnt[e], 0u);
             if (c != 0u)
                 update(e, c);
@@ -241,19 +268,46 @@ __device__ __forceinline__ long long nt_take_sum(unsigned long long *__restrict_
     return (long long)atomicExch(&acc[e], 0ull);
 }
 
+// The staged update's push (r48_ntuple.h): the owner of entry e, whose new value is w, writes w to
+// the same entry of every stage above it up to the first owned one. Every mark of this update was
+// set by the launch before, so a stage that the update touches is owned and is never written here;
+// an unowned one has exactly one writer, the owner of the nearest owned stage below it. A board of
+// the top stage pushes nothing. Only the staged kernels hold this code.
+template <int L>
+__device__ __forceinline__ void nt_push(float *tables, const uint8_t *own, uint32_t e, const r48::NtLayout &lay,
+                                        const r48::NtCuts &cuts, float w)
+{
+    const uint32_t size = (uint32_t)lay.m << (4 * L), end = (uint32_t)(cuts.n + 1) * size;   // <= 2^29
+    for (uint32_t k = e + size; k < end && own[k] == 0; k += size)
+        tables[k] = w;
+}
+
 // The owner moves tables[e] by step * the mean delta of the entry's hits, once. No float atomics:
 // bitwise reproducible.
-template <int L>
+template <int L, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_apply(const int8_t *__restrict__ boards, int64_t n,
                                                      const uint8_t *__restrict__ valid, const r48::NtLayout lay,
                                                      float step, float *__restrict__ tables,
-                                                     unsigned long long *__restrict__ acc, uint32_t *__restrict__ cnt)
+                                                     unsigned long long *__restrict__ acc, uint32_t *__restrict__ cnt,
+                                                     const C... cuts)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n || (valid && !valid[i]))
         return;
-    nt_owned_hits<L>(r48::nt_pack(r48::load_board(boards, i)), lay, cnt,
-                     [&](uint32_t e, uint32_t c) { tables[e] += step * r48::nt_mean(nt_take_sum(acc, e), c); });
+    const r48::Board b = r48::load_board(boards, i);
+    nt_owned_hits<L>(
+        r48::nt_pack(b), lay, cnt,
+        [&](uint32_t e, uint32_t c) {
+            if constexpr (sizeof...(C) == 0) {
+                tables[e] += step * r48::nt_mean(nt_take_sum(acc, e), c);
+            } else {
+                float w = tables[e];
+                w += step * r48::nt_mean(nt_take_sum(acc, e), c);
+                tables[e] = w;
+                nt_push<L>(tables, nt_own(cuts...), e, lay, nt_stg(cuts...), w);
+            }
+        },
+        r48::nt_base<L>(nt_stg(cuts...), lay.m, b));
 }
 
 // apply with temporal-coherence learning rates (r48_ntuple.h): the owner of an entry also owns
@@ -261,36 +315,44 @@ __global__ __launch_bounds__(kBlock) void k_nt_apply(const int8_t *__restrict__ 
 // three plain stores follow. The sums are order-free integers and the owner's arithmetic does not
 // depend on which lane it is, so all three tables are bitwise reproducible and independent of the
 // boards' order in the batch.
-template <int L>
+template <int L, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_apply_tc(const int8_t *__restrict__ boards, int64_t n,
                                                         const uint8_t *__restrict__ valid, const r48::NtLayout lay,
                                                         float step, float *__restrict__ tables,
                                                         float *__restrict__ tc_e, float *__restrict__ tc_a,
                                                         unsigned long long *__restrict__ acc,
-                                                        uint32_t *__restrict__ cnt)
+                                                        uint32_t *__restrict__ cnt, const C... cuts)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n || (valid && !valid[i]))
         return;
-    nt_owned_hits<L>(r48::nt_pack(r48::load_board(boards, i)), lay, cnt, [&](uint32_t e, uint32_t c) {
-        float w = tables[e], se = tc_e[e], sa = tc_a[e];
-        r48::nt_tc_update(w, se, sa, r48::nt_mean(nt_take_sum(acc, e), c), step);
-        tables[e] = w;
-        tc_e[e] = se;
-        tc_a[e] = sa;
-    });
+    const r48::Board b = r48::load_board(boards, i);
+    nt_owned_hits<L>(
+        r48::nt_pack(b), lay, cnt,
+        [&](uint32_t e, uint32_t c) {
+            float w = tables[e], se = tc_e[e], sa = tc_a[e];
+            r48::nt_tc_update(w, se, sa, r48::nt_mean(nt_take_sum(acc, e), c), step);
+            tables[e] = w;
+            tc_e[e] = se;
+            tc_a[e] = sa;
+            if constexpr (sizeof...(C) != 0)   // the value alone: a promoted entry's first update runs at rate 1
+                nt_push<L>(tables, nt_own(cuts...), e, lay, nt_stg(cuts...), w);
+        },
+        r48::nt_base<L>(nt_stg(cuts...), lay.m, b));
 }
 
 // How settled the network is on a set of boards: the mean learning rate over each board's hits.
-template <int L>
+template <int L, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_tc_rate(const int8_t *__restrict__ boards, int64_t n,
                                                        const r48::NtLayout lay, const float *__restrict__ tc_e,
-                                                       const float *__restrict__ tc_a, float *__restrict__ rate_out)
+                                                       const float *__restrict__ tc_a, float *__restrict__ rate_out,
+                                                       const C... cuts)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
         return;
-    rate_out[i] = r48::nt_tc_rate_mean<L>(r48::nt_pack(r48::load_board(boards, i)), lay, tc_e, tc_a);
+    const r48::Board b = r48::load_board(boards, i);
+    rate_out[i] = r48::nt_tc_rate_mean<L>(r48::nt_pack(b), lay, tc_e, tc_a, r48::nt_base<L>(nt_stg(cuts...), lay.m, b));
 }
 
 // The expectimax search of r48_ntuple.h, one board per wave: lane = 16 a + c is (move a, cell c).
@@ -356,9 +418,9 @@ __device__ __forceinline__ float nt_slot_term(float leaf0, float leaf1, uint32_t
 // lane's Q_2 of its row's move (-inf where the move is illegal) and the board's legal set. Shared
 // by k_nt_search<L, 2>, whose board is the batch's, and k_nt_search3, whose boards are the root's
 // children.
-template <int L>
+template <int L, class Stg>
 __device__ __forceinline__ float nt_wave_q2(const r48::Board &b, uint32_t lane, const r48::NtLayout &lay,
-                                            const float *__restrict__ tables, uint32_t &lg)
+                                            const float *__restrict__ tables, uint32_t &lg, const Stg &stg)
 {
     const uint32_t a = lane >> 4, c = lane & 15u;
     const r48::Moves4 m = r48::move_rows4<true>(b);
@@ -378,7 +440,7 @@ __device__ __forceinline__ float nt_wave_q2(const r48::Board &b, uint32_t lane, 
             const uint32_t p = r48::nt_select_bit(M, (base + lane) >> 1);
             r48::Board child = r48::nt_pick(m, p >> 4);
             r48::place(child, p & 15u, 1u + (lane & 1u), true);
-            leaf = r48::nt_leaf<L>(child, lay, tables);
+            leaf = r48::nt_leaf<L>(child, lay, tables, stg);
         }
         leaf0 = base == 0u ? leaf : leaf0;
         leaf1 = base == 0u ? leaf1 : leaf;
@@ -388,9 +450,9 @@ __device__ __forceinline__ float nt_wave_q2(const r48::Board &b, uint32_t lane, 
 
 // The depth-1 search in the same lane mapping: the first lane of a row scores s_a itself, the row
 // reads it. Shared by k_nt_search<L, 1> and k_nt_search_ruled.
-template <int L>
+template <int L, class Stg>
 __device__ __forceinline__ float nt_wave_q1(const r48::Board &b, uint32_t lane, const r48::NtLayout &lay,
-                                            const float *__restrict__ tables, uint32_t &lg)
+                                            const float *__restrict__ tables, uint32_t &lg, const Stg &stg)
 {
     const uint32_t a = lane >> 4, c = lane & 15u;
     const r48::Moves4 m = r48::move_rows4<true>(b);
@@ -398,7 +460,7 @@ __device__ __forceinline__ float nt_wave_q1(const r48::Board &b, uint32_t lane, 
     const bool ok = ((lg >> a) & 1u) != 0u;
     float x = 0.0f;
     if (ok && c == 0u)
-        x = r48::nt_score<L>(r48::nt_pick(m, a), r48::nt_pick_reward(m, a), lay, tables);
+        x = r48::nt_score<L>(r48::nt_pick(m, a), r48::nt_pick_reward(m, a), lay, tables, stg);
     return ok ? __shfl(x, (int)(lane & 48u)) : -__builtin_inff();
 }
 
@@ -427,9 +489,10 @@ struct WaveRoot {
 // 100 to 168 VGPRs): the first lane of each row leaves its afterstate in the wave's own LDS slot
 // `keep`, the loop reads a child's parent from there with a uniform address and the tail its
 // row's. Only this wave touches `keep`, and a wave's LDS operations complete in order.
-template <int L>
+template <int L, class Stg>
 __device__ __forceinline__ float nt_wave_q3(const r48::Board &b, uint32_t lane, const r48::NtLayout &lay,
-                                            const float *__restrict__ tables, WaveRoot &keep, uint32_t &lg)
+                                            const float *__restrict__ tables, WaveRoot &keep, uint32_t &lg,
+                                            const Stg &stg)
 {
     const uint32_t a = lane >> 4, c = lane & 15u;
     uint64_t M;
@@ -458,7 +521,7 @@ __device__ __forceinline__ float nt_wave_q3(const r48::Board &b, uint32_t lane, 
         r48::Board child{sa[0], sa[1], sa[2], sa[3]};
         r48::place(child, p & 15u, 1u + (j & 1u), true);
         uint32_t lg2;
-        const float q2a = nt_wave_q2<L>(child, lane, lay, tables, lg2);
+        const float q2a = nt_wave_q2<L>(child, lane, lay, tables, lg2, stg);
         const float best = nt_wave_best(q2a, uniform_word(lg2));
         const bool mine = lane == (j & 63u);
         leaf0 = (mine && j < 64u) ? best : leaf0;
@@ -471,11 +534,11 @@ __device__ __forceinline__ float nt_wave_q3(const r48::Board &b, uint32_t lane, 
     return nt_row_q(nt_slot_term(leaf0, leaf1, rank2, slot), ok, keep.reward[a], s);
 }
 
-template <int L, int DEPTH>
+template <int L, int DEPTH, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_search(const int8_t *__restrict__ boards, int64_t n,
                                                       const r48::NtLayout lay, const float *__restrict__ tables,
                                                       int8_t *__restrict__ actions, float *__restrict__ q,
-                                                      uint8_t *__restrict__ legal)
+                                                      uint8_t *__restrict__ legal, const C... cuts)
 {
     static_assert(DEPTH == 1 || DEPTH == 2, "depth 1 or 2");
     const int64_t i = (int64_t)blockIdx.x * kSearchBoards + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -486,9 +549,9 @@ __global__ __launch_bounds__(kBlock) void k_nt_search(const int8_t *__restrict__
     uint32_t lg;
     float qa;
     if (DEPTH == 1)
-        qa = nt_wave_q1<L>(b, lane, lay, tables, lg);
+        qa = nt_wave_q1<L>(b, lane, lay, tables, lg, nt_stg(cuts...));
     else
-        qa = nt_wave_q2<L>(b, lane, lay, tables, lg);
+        qa = nt_wave_q2<L>(b, lane, lay, tables, lg, nt_stg(cuts...));
     nt_write_search(qa, lane, lg, i, actions, q, legal);
 }
 
@@ -561,10 +624,10 @@ __device__ __forceinline__ void nt_root_moves(const r48::Board &b, uint32_t lane
 // nt_select_bit(M, j >> 1), its parent afterstate read from `root` with a uniform address) searched
 // INNER plies deep -- 2: nt_wave_q2, 3: nt_wave_q3 with the wave's own LDS slot -- and best_INNER of
 // it in every lane. The per-child body of nt_deal_and_finish and of k_nt_play_ruled.
-template <int L, int INNER>
+template <int L, int INNER, class Stg>
 __device__ __forceinline__ float nt_child_best(const Search3Root &root, uint64_t M, uint32_t j, uint32_t lane,
                                                const r48::NtLayout &lay, const float *__restrict__ tables,
-                                               WaveRoot *keep_w)
+                                               WaveRoot *keep_w, const Stg &stg)
 {
     static_assert(INNER == 2 || INNER == 3, "a child is searched 2 or 3 plies deep");
     const uint32_t p = r48::nt_select_bit(M, j >> 1);   // < 64
@@ -574,9 +637,9 @@ __device__ __forceinline__ float nt_child_best(const Search3Root &root, uint64_t
     uint32_t lgc;
     float qc;
     if constexpr (INNER == 2)
-        qc = nt_wave_q2<L>(child, lane, lay, tables, lgc);
+        qc = nt_wave_q2<L>(child, lane, lay, tables, lgc, stg);
     else
-        qc = nt_wave_q3<L>(child, lane, lay, tables, *keep_w, lgc);
+        qc = nt_wave_q3<L>(child, lane, lay, tables, *keep_w, lgc, stg);
     return nt_wave_best(qc, lgc);
 }
 
@@ -603,11 +666,11 @@ __device__ __forceinline__ float nt_finish_rows(const Search3Root &root, const f
 // board's Q_3, k_nt_search3 and the ruled kernel at depth 3) or 3 (nt_wave_q3 with the wave's LDS
 // slot `keep`; the board's Q_4). Nothing follows it in a kernel: a wave returns from it when it
 // has no more to do.
-template <int L, int WAVES, int INNER>
+template <int L, int WAVES, int INNER, class Stg>
 __device__ __forceinline__ void nt_deal_and_finish(Search3Root &root, float *leaf, WaveRoot *keep, int64_t i, uint32_t w,
                                                    uint32_t lane, const r48::NtLayout &lay,
                                                    const float *__restrict__ tables, int8_t *__restrict__ actions,
-                                                   float *__restrict__ q, uint8_t *__restrict__ legal)
+                                                   float *__restrict__ q, uint8_t *__restrict__ legal, const Stg &stg)
 {
     static_assert(INNER == 2 || INNER == 3, "a child is searched 2 or 3 plies deep");
     const uint32_t a = lane >> 4, c = lane & 15u;
@@ -627,7 +690,7 @@ __device__ __forceinline__ void nt_deal_and_finish(Search3Root &root, float *lea
     uint32_t mine = 0u;
 #pragma unroll 1
     for (uint32_t j = w; j < kids; mine++) {
-        const float best = nt_child_best<L, INNER>(root, M, j, lane, lay, tables, keep + w);
+        const float best = nt_child_best<L, INNER>(root, M, j, lane, lay, tables, keep + w, stg);
         uint32_t next = 0u;
         if (lane == 0u) {
             leaf[j] = best;
@@ -645,11 +708,11 @@ __device__ __forceinline__ void nt_deal_and_finish(Search3Root &root, float *lea
     nt_write_search(nt_finish_rows(root, leaf, M, lg, lane), lane, lg, i, actions, q, legal);
 }
 
-template <int L, int WAVES>
+template <int L, int WAVES, class... C>
 __global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restrict__ boards, int64_t n,
                                                            const r48::NtLayout lay, const float *__restrict__ tables,
                                                            int8_t *__restrict__ actions, float *__restrict__ q,
-                                                           uint8_t *__restrict__ legal)
+                                                           uint8_t *__restrict__ legal, const C... cuts)
 {
     static_assert(WAVES >= 1 && WAVES <= 16, "a workgroup has at most 1024 lanes");
     __shared__ float leaf[kSearch3MaxKids];
@@ -660,7 +723,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restr
     if (w == 0u)
         nt_root_moves<WAVES>(r48::load_board(boards, i), lane, root);
     __syncthreads();
-    nt_deal_and_finish<L, WAVES, 2>(root, leaf, nullptr, i, w, lane, lay, tables, actions, q, legal);
+    nt_deal_and_finish<L, WAVES, 2>(root, leaf, nullptr, i, w, lane, lay, tables, actions, q, legal, nt_stg(cuts...));
 }
 
 // The ruled search of r48_ntuple.h: board i at depth d = rule[blanks(board i)], 1..4, one board per
@@ -673,12 +736,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_search3(const int8_t *__restr
 //   d <= 2  wave 0 alone runs k_nt_search's depth-2 or depth-1 body on the board it still holds;
 //           the other waves leave after the barrier
 // The rule travels as one word (nt_rule_pack). depth_out[i] = d whether the board has a move or not.
-template <int L, int WAVES>
+template <int L, int WAVES, class... C>
 __global__ __launch_bounds__(64 * WAVES) void k_nt_search_ruled(const int8_t *__restrict__ boards, int64_t n,
                                                                 const r48::NtLayout lay, const float *__restrict__ tables,
                                                                 const uint64_t rule, int8_t *__restrict__ actions,
                                                                 float *__restrict__ q, uint8_t *__restrict__ legal,
-                                                                uint8_t *__restrict__ depth_out)
+                                                                uint8_t *__restrict__ depth_out, const C... cuts)
 {
     static_assert(WAVES >= 1 && WAVES <= 16, "a workgroup has at most 1024 lanes");
     __shared__ float leaf[kSearch3MaxKids];
@@ -703,12 +766,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_search_ruled(const int8_t *__
     __syncthreads();
     const uint32_t d = uniform_word(depth);
     if (d == 4u) {
-        nt_deal_and_finish<L, WAVES, 3>(root, leaf, keep, i, w, lane, lay, tables, actions, q, legal);
+        nt_deal_and_finish<L, WAVES, 3>(root, leaf, keep, i, w, lane, lay, tables, actions, q, legal, nt_stg(cuts...));
     } else if (d == 3u) {
-        nt_deal_and_finish<L, WAVES, 2>(root, leaf, keep, i, w, lane, lay, tables, actions, q, legal);
+        nt_deal_and_finish<L, WAVES, 2>(root, leaf, keep, i, w, lane, lay, tables, actions, q, legal, nt_stg(cuts...));
     } else if (w == 0u) {
         uint32_t lg;
-        const float qa = d == 2u ? nt_wave_q2<L>(b, lane, lay, tables, lg) : nt_wave_q1<L>(b, lane, lay, tables, lg);
+        const float qa = d == 2u ? nt_wave_q2<L>(b, lane, lay, tables, lg, nt_stg(cuts...))
+                                 : nt_wave_q1<L>(b, lane, lay, tables, lg, nt_stg(cuts...));
         nt_write_search(qa, lane, lg, i, actions, q, legal);
     }
 }
@@ -751,12 +815,12 @@ __device__ __forceinline__ void nt_play_store(int8_t *__restrict__ boards, int64
 #endif
 constexpr int kPlayLanes = R48_NT_PLAY_LANES;
 
-template <int L, int LANES>
+template <int L, int LANES, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_play1(int8_t *__restrict__ boards, int64_t n, const r48::NtLayout lay,
                                                      const float *__restrict__ tables, int32_t n_steps, uint32_t k0,
                                                      uint32_t k1, int64_t gid0, uint32_t step0,
                                                      int32_t *__restrict__ length, int32_t *__restrict__ gain,
-                                                     uint8_t *__restrict__ done)
+                                                     uint8_t *__restrict__ done, const C... cuts)
 {
     static_assert(LANES == 1 || LANES == 4, "one lane per board, or one per move");
     const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
@@ -774,7 +838,7 @@ __global__ __launch_bounds__(kBlock) void k_nt_play1(int8_t *__restrict__ boards
         if (alive) {
             uint32_t action, lg;
             if (LANES == 1) {
-                const NtMove mv = nt_act_board<L>(b, lay, tables);
+                const NtMove mv = nt_act_board<L>(b, lay, tables, nt_stg(cuts...));
                 action = mv.action;
                 lg = mv.legal;
             } else {
@@ -782,7 +846,7 @@ __global__ __launch_bounds__(kBlock) void k_nt_play1(int8_t *__restrict__ boards
                 lg = r48::nt_legal4(m, b);
                 float s = 0.0f;
                 if ((lg >> sub) & 1u)
-                    s = r48::nt_score<L>(r48::nt_pick(m, sub), r48::nt_pick_reward(m, sub), lay, tables);
+                    s = r48::nt_score<L>(r48::nt_pick(m, sub), r48::nt_pick_reward(m, sub), lay, tables, nt_stg(cuts...));
                 const int first = (int)(threadIdx.x & 63u & ~3u);
                 action = 0u;
                 float best = 0.0f;
@@ -815,12 +879,12 @@ __global__ __launch_bounds__(kBlock) void k_nt_play1(int8_t *__restrict__ boards
 // it, the rows' scores are read as nt_write_search reads them and every lane takes their first
 // maximiser and makes the same step, so the board stays wave-uniform; lane 0 stores it once at the
 // end.
-template <int L>
+template <int L, class... C>
 __global__ __launch_bounds__(kBlock) void k_nt_play2(int8_t *__restrict__ boards, int64_t n, const r48::NtLayout lay,
                                                      const float *__restrict__ tables, int32_t n_steps, uint32_t k0,
                                                      uint32_t k1, int64_t gid0, uint32_t step0,
                                                      int32_t *__restrict__ length, int32_t *__restrict__ gain,
-                                                     uint8_t *__restrict__ done)
+                                                     uint8_t *__restrict__ done, const C... cuts)
 {
     const int64_t i = (int64_t)blockIdx.x * kSearchBoards + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (i >= n)
@@ -832,7 +896,7 @@ __global__ __launch_bounds__(kBlock) void k_nt_play2(int8_t *__restrict__ boards
 #pragma unroll 1
     for (int32_t t = 0; t < n_steps; t++) {
         uint32_t lg;
-        const float qa = nt_wave_q2<L>(b, lane, lay, tables, lg);
+        const float qa = nt_wave_q2<L>(b, lane, lay, tables, lg, nt_stg(cuts...));
         if (uniform_word(lg) == 0u)
             break;   // finished: the wave leaves
         const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 16), q2 = __shfl(qa, 32), q3 = __shfl(qa, 48);
@@ -900,13 +964,13 @@ struct PlayHand {
     uint32_t t, alive;
 };
 
-template <int L, int WAVES>
+template <int L, int WAVES, class... C>
 __global__ __launch_bounds__(64 * WAVES) void k_nt_play_ruled(int8_t *__restrict__ boards, int64_t n,
                                                               const r48::NtLayout lay, const float *__restrict__ tables,
                                                               const uint64_t rule, int32_t n_steps, uint32_t k0,
                                                               uint32_t k1, int64_t gid0, uint32_t step0,
                                                               int32_t *__restrict__ length, int32_t *__restrict__ gain,
-                                                              uint8_t *__restrict__ done)
+                                                              uint8_t *__restrict__ done, const C... cuts)
 {
     static_assert(WAVES >= 1 && WAVES <= 16, "a workgroup has at most 1024 lanes");
     __shared__ float leaf[2][kSearch3MaxKids];
@@ -932,7 +996,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_play_ruled(int8_t *__restrict
 #pragma unroll 1
                 do {
                     uint32_t lg;
-                    const float qa = d == 2u ? nt_wave_q2<L>(b, lane, lay, tables, lg) : nt_wave_q1<L>(b, lane, lay, tables, lg);
+                    const float qa = d == 2u ? nt_wave_q2<L>(b, lane, lay, tables, lg, nt_stg(cuts...))
+                                             : nt_wave_q1<L>(b, lane, lay, tables, lg, nt_stg(cuts...));
                     if (uniform_word(lg) == 0u) {
                         alive = 0u;   // finished
                         break;
@@ -982,8 +1047,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_play_ruled(int8_t *__restrict
         const uint32_t kids = 2u * (uint32_t)__popcll(M);   // 4 .. 120
 #pragma unroll 1
         for (uint32_t j = w; j < kids;) {   // a wave's own loop: it ends at B2 however many children it took, none included
-            const float best = d == 4u ? nt_child_best<L, 3>(rt, M, j, lane, lay, tables, keep + w)
-                                       : nt_child_best<L, 2>(rt, M, j, lane, lay, tables, keep + w);
+            const float best = d == 4u ? nt_child_best<L, 3>(rt, M, j, lane, lay, tables, keep + w, nt_stg(cuts...))
+                                       : nt_child_best<L, 2>(rt, M, j, lane, lay, tables, keep + w, nt_stg(cuts...));
             uint32_t next = 0u;
             if (lane == 0u) {
                 lf[j] = best;   // j < kids <= kSearch3MaxKids
@@ -1061,42 +1126,82 @@ void launch(Kernel kernel, dim3 grid, dim3 block, void *stream, const A &...args
 
 unsigned long long *words(int64_t *acc) { return reinterpret_cast<unsigned long long *>(acc); }
 
-}  // namespace
+// The staging of one call: off for the plain entry points and for n_cuts == 0, which run the
+// unstaged kernels; else the checked cuts as the staged kernels take them.
+struct Staging {
+    bool on = false;
+    r48::NtCuts cuts{0u, 0};
+    NtCutsOwn upd{{0u, 0}, nullptr};
+};
 
-extern "C" {
+// What every staged entry point checks after check_args: the cuts, and own where it updates.
+int check_cuts(const char *fn, const uint8_t *cuts, int32_t n_cuts, bool updates, uint8_t *own, Staging &st)
+{
+    if (const char *why = r48::nt_cuts_check(cuts, n_cuts))
+        return fail(R48_EINVAL, std::string(fn) + ": bad cuts: " + why);
+    if (updates && n_cuts > 0 && !own)
+        return fail(R48_EINVAL, std::string(fn) + ": own is NULL");
+    st.on = n_cuts > 0;
+    st.cuts = r48::nt_cuts_pack(cuts, n_cuts);
+    st.upd = NtCutsOwn{st.cuts, own};
+    return R48_OK;
+}
 
-int r48_ntuple_value(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
-                     float *value, void *stream)
+// the unstaged kernel with its arguments, or its staged twin with x (the cuts) behind them
+template <class Plain, class Staged, class X, class... A>
+void launch2(bool staged, Plain plain, Staged twin, dim3 grid, dim3 block, void *stream, const X &x, const A &...args)
+{
+    if (staged)
+        launch(twin, grid, block, stream, args..., x);
+    else
+        launch(plain, grid, block, stream, args...);
+}
+
+// ---- one body per pair of entry points: fn is the name in the messages, cuts / n_cuts / own are
+// NULL / 0 / NULL from the plain one --------------------------------------------------------------
+
+int nt_value(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+             const uint8_t *cuts, int32_t n_cuts, const float *tables, float *value, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_value", boards, n, cells, m, L, lay,
-                                  {{"tables", tables, 4, true}, {"value", value, 4, true}}))
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay, {{"tables", tables, 4, true}, {"value", value, 4, true}}))
+        return rc;
+    if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
         return rc;
     return run("k_nt_value", n, lay.L, [&](auto len) {
-        launch(k_nt_value<len()>, grid_for(n), kBlock, stream, boards, n, lay, tables, value);
+        launch2(st.on, k_nt_value<len()>, k_nt_value<len(), r48::NtCuts>, grid_for(n), kBlock, stream, st.cuts, boards, n,
+                lay, tables, value);
     });
 }
 
-int r48_ntuple_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
-                   int8_t *actions, int8_t *after, float *value, int32_t *reward, uint8_t *legal, void *stream)
+int nt_act(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+           const uint8_t *cuts, int32_t n_cuts, const float *tables, int8_t *actions, int8_t *after, float *value,
+           int32_t *reward, uint8_t *legal, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_act", boards, n, cells, m, L, lay,
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
                                   {{"tables", tables, 4, true}, {"actions", actions, 1, true}, {"after", after, 16, false},
                                    {"value", value, 4, false}, {"reward", reward, 4, false}}))
         return rc;
+    if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
+        return rc;
     return run("k_nt_act", n, lay.L, [&](auto len) {
-        launch(k_nt_act<len()>, grid_for(n), kBlock, stream, boards, n, lay, tables, actions, after, value, reward, legal);
+        launch2(st.on, k_nt_act<len()>, k_nt_act<len(), r48::NtCuts>, grid_for(n), kBlock, stream, st.cuts, boards, n, lay,
+                tables, actions, after, value, reward, legal);
     });
 }
 
-int r48_ntuple_td_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
-                      const int8_t *prev_after, const float *prev_value, const uint8_t *prev_done,
-                      const uint8_t *prev_valid, int8_t *actions, int8_t *after, float *value, int32_t *reward,
-                      uint8_t *legal, uint8_t *valid_out, float *delta_out, int64_t *acc, uint32_t *cnt, void *stream)
+int nt_td_act(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+              const uint8_t *cuts, int32_t n_cuts, const float *tables, const int8_t *prev_after, const float *prev_value,
+              const uint8_t *prev_done, const uint8_t *prev_valid, int8_t *actions, int8_t *after, float *value,
+              int32_t *reward, uint8_t *legal, uint8_t *valid_out, float *delta_out, int64_t *acc, uint32_t *cnt,
+              uint8_t *own, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_td_act", boards, n, cells, m, L, lay,
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
                                   {{"tables", tables, 4, true}, {"prev_after", prev_after, 16, true},
                                    {"prev_value", prev_value, 4, true}, {"prev_done", prev_done, 1, true},
                                    {"prev_valid", prev_valid, 1, true}, {"actions", actions, 1, true},
@@ -1105,128 +1210,153 @@ int r48_ntuple_td_act(const int8_t *boards, int64_t n, const uint8_t *cells, int
                                    {"delta_out", delta_out, 4, false}, {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
         return rc;
     if (after == prev_after || value == prev_value || valid_out == prev_valid)
-        return fail(R48_EINVAL, "r48_ntuple_td_act: after, value and valid_out must not be the prev_ buffers (apply "
-                                "reads the previous afterstates and flags after this call; swap the buffers then)");
+        return fail(R48_EINVAL, std::string(fn) + ": after, value and valid_out must not be the prev_ buffers (apply "
+                                                  "reads the previous afterstates and flags after this call; swap the buffers then)");
+    if (const int rc = check_cuts(fn, cuts, n_cuts, true, own, st))
+        return rc;
     return run("k_nt_td_act", n, lay.L, [&](auto len) {
-        launch(k_nt_td_act<len()>, grid_for(n), kBlock, stream, boards, n, lay, tables, prev_after, prev_value, prev_done,
-               prev_valid, actions, after, value, reward, legal, valid_out, delta_out, words(acc), cnt);
+        launch2(st.on, k_nt_td_act<len()>, k_nt_td_act<len(), NtCutsOwn>, grid_for(n), kBlock, stream, st.upd, boards, n, lay,
+                tables, prev_after, prev_value, prev_done, prev_valid, actions, after, value, reward, legal, valid_out,
+                delta_out, words(acc), cnt);
     });
 }
 
-int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
-                      int32_t depth, int8_t *actions, float *q, uint8_t *legal, void *stream)
+int nt_search(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+              const uint8_t *cuts, int32_t n_cuts, const float *tables, int32_t depth, int8_t *actions, float *q,
+              uint8_t *legal, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_search", boards, n, cells, m, L, lay,
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
                                   {{"tables", tables, 4, true}, {"actions", actions, 1, true}, {"q", q, 4, false}}))
         return rc;
     if (depth != 1 && depth != 2)
-        return fail(R48_EINVAL, "r48_ntuple_search: depth must be 1 or 2, got " + std::to_string(depth));
+        return fail(R48_EINVAL, std::string(fn) + ": depth must be 1 or 2, got " + std::to_string(depth));
     const int64_t blocks = n / kSearchBoards + (n % kSearchBoards ? 1 : 0);   // one board per wave
     if (blocks > 0x7FFFFFFFll)
-        return fail(R48_EINVAL, "r48_ntuple_search: n = " + std::to_string(n) + " boards exceed the grid (" +
+        return fail(R48_EINVAL, std::string(fn) + ": n = " + std::to_string(n) + " boards exceed the grid (" +
                                     std::to_string(kSearchBoards) + " boards per workgroup, 2^31 - 1 workgroups)");
+    if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
+        return rc;
     const dim3 grid((unsigned)blocks);
     return run("k_nt_search", n, lay.L, [&](auto len) {
         if (depth == 1)
-            launch(k_nt_search<len(), 1>, grid, kBlock, stream, boards, n, lay, tables, actions, q, legal);
+            launch2(st.on, k_nt_search<len(), 1>, k_nt_search<len(), 1, r48::NtCuts>, grid, kBlock, stream, st.cuts, boards,
+                    n, lay, tables, actions, q, legal);
         else
-            launch(k_nt_search<len(), 2>, grid, kBlock, stream, boards, n, lay, tables, actions, q, legal);
+            launch2(st.on, k_nt_search<len(), 2>, k_nt_search<len(), 2, r48::NtCuts>, grid, kBlock, stream, st.cuts, boards,
+                    n, lay, tables, actions, q, legal);
     });
 }
 
-int r48_ntuple_search3(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
-                       const float *tables, int8_t *actions, float *q, uint8_t *legal, void *stream)
+int nt_search3(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+               const uint8_t *cuts, int32_t n_cuts, const float *tables, int8_t *actions, float *q, uint8_t *legal,
+               void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_search3", boards, n, cells, m, L, lay,
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
                                   {{"tables", tables, 4, true}, {"actions", actions, 1, true}, {"q", q, 4, false}}))
         return rc;
     if (n > 0x7FFFFFFFll)   // one board per workgroup
-        return fail(R48_EINVAL, "r48_ntuple_search3: n = " + std::to_string(n) +
+        return fail(R48_EINVAL, std::string(fn) + ": n = " + std::to_string(n) +
                                     " boards exceed the grid (one per workgroup, 2^31 - 1 workgroups)");
+    if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
+        return rc;
     const dim3 grid((unsigned)n);
     return run("k_nt_search3", n, lay.L, [&](auto len) {
         if (n <= kSearch3SmallBatch)
-            launch(k_nt_search3<len(), kSearch3WavesSmall>, grid, 64 * kSearch3WavesSmall, stream, boards, n, lay, tables,
-                   actions, q, legal);
+            launch2(st.on, k_nt_search3<len(), kSearch3WavesSmall>, k_nt_search3<len(), kSearch3WavesSmall, r48::NtCuts>,
+                    grid, 64 * kSearch3WavesSmall, stream, st.cuts, boards, n, lay, tables, actions, q, legal);
         else
-            launch(k_nt_search3<len(), kSearch3WavesLarge>, grid, 64 * kSearch3WavesLarge, stream, boards, n, lay, tables,
-                   actions, q, legal);
+            launch2(st.on, k_nt_search3<len(), kSearch3WavesLarge>, k_nt_search3<len(), kSearch3WavesLarge, r48::NtCuts>,
+                    grid, 64 * kSearch3WavesLarge, stream, st.cuts, boards, n, lay, tables, actions, q, legal);
     });
 }
 
-int r48_ntuple_search_ruled(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
-                            const float *tables, const uint8_t *rule, int8_t *actions, float *q, uint8_t *legal,
-                            uint8_t *depth_out, void *stream)
+int nt_search_ruled(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                    const uint8_t *cuts, int32_t n_cuts, const float *tables, const uint8_t *rule, int8_t *actions,
+                    float *q, uint8_t *legal, uint8_t *depth_out, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_search_ruled", boards, n, cells, m, L, lay,
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
                                   {{"tables", tables, 4, true}, {"actions", actions, 1, true}, {"q", q, 4, false}}))
         return rc;
     if (const char *why = r48::nt_rule_check(rule))
-        return fail(R48_EINVAL, std::string("r48_ntuple_search_ruled: bad rule: ") + why);
+        return fail(R48_EINVAL, std::string(fn) + ": bad rule: " + why);
     if (n > 0x7FFFFFFFll)   // one board per workgroup
-        return fail(R48_EINVAL, "r48_ntuple_search_ruled: n = " + std::to_string(n) +
+        return fail(R48_EINVAL, std::string(fn) + ": n = " + std::to_string(n) +
                                     " boards exceed the grid (one per workgroup, 2^31 - 1 workgroups)");
+    if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
+        return rc;
     const uint64_t packed = r48::nt_rule_pack(rule);
     const dim3 grid((unsigned)n);
     return run("k_nt_search_ruled", n, lay.L, [&](auto len) {
         if (n <= kSearch3SmallBatch)
-            launch(k_nt_search_ruled<len(), kSearch3WavesSmall>, grid, 64 * kSearch3WavesSmall, stream, boards, n, lay,
-                   tables, packed, actions, q, legal, depth_out);
+            launch2(st.on, k_nt_search_ruled<len(), kSearch3WavesSmall>,
+                    k_nt_search_ruled<len(), kSearch3WavesSmall, r48::NtCuts>, grid, 64 * kSearch3WavesSmall, stream, st.cuts,
+                    boards, n, lay, tables, packed, actions, q, legal, depth_out);
         else
-            launch(k_nt_search_ruled<len(), kSearch3WavesLarge>, grid, 64 * kSearch3WavesLarge, stream, boards, n, lay,
-                   tables, packed, actions, q, legal, depth_out);
+            launch2(st.on, k_nt_search_ruled<len(), kSearch3WavesLarge>,
+                    k_nt_search_ruled<len(), kSearch3WavesLarge, r48::NtCuts>, grid, 64 * kSearch3WavesLarge, stream, st.cuts,
+                    boards, n, lay, tables, packed, actions, q, legal, depth_out);
     });
 }
 
-int r48_ntuple_play(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
-                    int32_t depth, int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step, int32_t *length,
-                    int32_t *gain, uint8_t *done, void *stream)
+int nt_play(const char *fn, int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const uint8_t *cuts,
+            int32_t n_cuts, const float *tables, int32_t depth, int32_t n_steps, uint64_t env_seed, int64_t gid0,
+            uint32_t env_step, int32_t *length, int32_t *gain, uint8_t *done, void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_play", boards, n, cells, m, L, lay,
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
                                   {{"tables", tables, 4, true}, {"length", length, 4, false}, {"gain", gain, 4, false}}))
         return rc;
     if (depth != 1 && depth != 2)
-        return fail(R48_EINVAL, "r48_ntuple_play: depth must be 1 or 2, got " + std::to_string(depth));
+        return fail(R48_EINVAL, std::string(fn) + ": depth must be 1 or 2, got " + std::to_string(depth));
     if (n_steps < 0)
-        return fail(R48_EINVAL, "r48_ntuple_play: n_steps must not be negative, got " + std::to_string(n_steps));
+        return fail(R48_EINVAL, std::string(fn) + ": n_steps must not be negative, got " + std::to_string(n_steps));
     const int64_t per = depth == 2 ? kSearchBoards : kBlock / kPlayLanes;   // boards per workgroup
     const int64_t blocks = n / per + (n % per ? 1 : 0);
     if (blocks > 0x7FFFFFFFll)
-        return fail(R48_EINVAL, "r48_ntuple_play: n = " + std::to_string(n) + " boards exceed the grid (" +
+        return fail(R48_EINVAL, std::string(fn) + ": n = " + std::to_string(n) + " boards exceed the grid (" +
                                     std::to_string(per) + " boards per workgroup, 2^31 - 1 workgroups)");
+    if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
+        return rc;
     if (n_steps == 0)
         return R48_OK;
     const dim3 grid((unsigned)blocks);
     const uint32_t k0 = (uint32_t)env_seed, k1 = (uint32_t)(env_seed >> 32);
     return run("k_nt_play", n, lay.L, [&](auto len) {
         if (depth == 1)
-            launch(k_nt_play1<len(), kPlayLanes>, grid, kBlock, stream, boards, n, lay, tables, n_steps, k0, k1, gid0,
-                   env_step, length, gain, done);
+            launch2(st.on, k_nt_play1<len(), kPlayLanes>, k_nt_play1<len(), kPlayLanes, r48::NtCuts>, grid, kBlock, stream,
+                    st.cuts, boards, n, lay, tables, n_steps, k0, k1, gid0, env_step, length, gain, done);
         else
-            launch(k_nt_play2<len()>, grid, kBlock, stream, boards, n, lay, tables, n_steps, k0, k1, gid0, env_step, length,
-                   gain, done);
+            launch2(st.on, k_nt_play2<len()>, k_nt_play2<len(), r48::NtCuts>, grid, kBlock, stream, st.cuts, boards, n, lay,
+                    tables, n_steps, k0, k1, gid0, env_step, length, gain, done);
     });
 }
 
-int r48_ntuple_play_ruled(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
-                          const uint8_t *rule, int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step,
-                          int32_t *length, int32_t *gain, uint8_t *done, void *stream)
+int nt_play_ruled(const char *fn, int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                  const uint8_t *cuts, int32_t n_cuts, const float *tables, const uint8_t *rule, int32_t n_steps,
+                  uint64_t env_seed, int64_t gid0, uint32_t env_step, int32_t *length, int32_t *gain, uint8_t *done,
+                  void *stream)
 {
     r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_play_ruled", boards, n, cells, m, L, lay,
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
                                   {{"tables", tables, 4, true}, {"length", length, 4, false}, {"gain", gain, 4, false}}))
         return rc;
     if (const char *why = r48::nt_rule_check(rule))
-        return fail(R48_EINVAL, std::string("r48_ntuple_play_ruled: bad rule: ") + why);
+        return fail(R48_EINVAL, std::string(fn) + ": bad rule: " + why);
     if (n_steps < 0)
-        return fail(R48_EINVAL, "r48_ntuple_play_ruled: n_steps must not be negative, got " + std::to_string(n_steps));
+        return fail(R48_EINVAL, std::string(fn) + ": n_steps must not be negative, got " + std::to_string(n_steps));
     if (n > 0x7FFFFFFFll)   // one board per workgroup
-        return fail(R48_EINVAL, "r48_ntuple_play_ruled: n = " + std::to_string(n) +
+        return fail(R48_EINVAL, std::string(fn) + ": n = " + std::to_string(n) +
                                     " boards exceed the grid (one per workgroup, 2^31 - 1 workgroups)");
+    if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
+        return rc;
     if (n_steps == 0)
         return R48_OK;
     const uint64_t packed = r48::nt_rule_pack(rule);
@@ -1234,63 +1364,264 @@ int r48_ntuple_play_ruled(int8_t *boards, int64_t n, const uint8_t *cells, int32
     const uint32_t k0 = (uint32_t)env_seed, k1 = (uint32_t)(env_seed >> 32);
     return run("k_nt_play_ruled", n, lay.L, [&](auto len) {
         if (n <= kSearch3SmallBatch)
-            launch(k_nt_play_ruled<len(), kPlayRuledWavesSmall>, grid, 64 * kPlayRuledWavesSmall, stream, boards, n, lay,
-                   tables, packed, n_steps, k0, k1, gid0, env_step, length, gain, done);
+            launch2(st.on, k_nt_play_ruled<len(), kPlayRuledWavesSmall>,
+                    k_nt_play_ruled<len(), kPlayRuledWavesSmall, r48::NtCuts>, grid, 64 * kPlayRuledWavesSmall, stream,
+                    st.cuts, boards, n, lay, tables, packed, n_steps, k0, k1, gid0, env_step, length, gain, done);
         else
-            launch(k_nt_play_ruled<len(), kPlayRuledWavesLarge>, grid, 64 * kPlayRuledWavesLarge, stream, boards, n, lay,
-                   tables, packed, n_steps, k0, k1, gid0, env_step, length, gain, done);
+            launch2(st.on, k_nt_play_ruled<len(), kPlayRuledWavesLarge>,
+                    k_nt_play_ruled<len(), kPlayRuledWavesLarge, r48::NtCuts>, grid, 64 * kPlayRuledWavesLarge, stream,
+                    st.cuts, boards, n, lay, tables, packed, n_steps, k0, k1, gid0, env_step, length, gain, done);
     });
+}
+
+int nt_accumulate(const char *fn, const int8_t *boards, int64_t n, const float *delta, const uint8_t *valid,
+                  const uint8_t *cells, int32_t m, int32_t L, const uint8_t *cuts, int32_t n_cuts, int64_t *acc,
+                  uint32_t *cnt, uint8_t *own, void *stream)
+{
+    r48::NtLayout lay;
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
+                                  {{"delta", delta, 4, true}, {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
+        return rc;
+    if (const int rc = check_cuts(fn, cuts, n_cuts, true, own, st))
+        return rc;
+    return run("k_nt_accumulate", n, lay.L, [&](auto len) {
+        launch2(st.on, k_nt_accumulate<len()>, k_nt_accumulate<len(), NtCutsOwn>, grid_for(n), kBlock, stream, st.upd, boards,
+                n, delta, valid, lay, words(acc), cnt);
+    });
+}
+
+int nt_apply(const char *fn, const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
+             int32_t L, const uint8_t *cuts, int32_t n_cuts, float step, float *tables, int64_t *acc, uint32_t *cnt,
+             uint8_t *own, void *stream)
+{
+    r48::NtLayout lay;
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
+        return rc;
+    if (const int rc = check_cuts(fn, cuts, n_cuts, true, own, st))
+        return rc;
+    return run("k_nt_apply", n, lay.L, [&](auto len) {
+        launch2(st.on, k_nt_apply<len()>, k_nt_apply<len(), NtCutsOwn>, grid_for(n), kBlock, stream, st.upd, boards, n, valid,
+                lay, step, tables, words(acc), cnt);
+    });
+}
+
+int nt_apply_tc(const char *fn, const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
+                int32_t L, const uint8_t *cuts, int32_t n_cuts, float step, float *tables, float *tc_e, float *tc_a,
+                int64_t *acc, uint32_t *cnt, uint8_t *own, void *stream)
+{
+    r48::NtLayout lay;
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"tc_e", tc_e, 4, true}, {"tc_a", tc_a, 4, true},
+                                   {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
+        return rc;
+    if (const int rc = check_cuts(fn, cuts, n_cuts, true, own, st))
+        return rc;
+    return run("k_nt_apply_tc", n, lay.L, [&](auto len) {
+        launch2(st.on, k_nt_apply_tc<len()>, k_nt_apply_tc<len(), NtCutsOwn>, grid_for(n), kBlock, stream, st.upd, boards, n,
+                valid, lay, step, tables, tc_e, tc_a, words(acc), cnt);
+    });
+}
+
+int nt_tc_rate(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+               const uint8_t *cuts, int32_t n_cuts, const float *tc_e, const float *tc_a, float *rate_out, void *stream)
+{
+    r48::NtLayout lay;
+    Staging st;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
+                                  {{"tc_e", tc_e, 4, true}, {"tc_a", tc_a, 4, true}, {"rate_out", rate_out, 4, true}}))
+        return rc;
+    if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
+        return rc;
+    return run("k_nt_tc_rate", n, lay.L, [&](auto len) {
+        launch2(st.on, k_nt_tc_rate<len()>, k_nt_tc_rate<len(), r48::NtCuts>, grid_for(n), kBlock, stream, st.cuts, boards, n,
+                lay, tc_e, tc_a, rate_out);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int r48_ntuple_value(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                     float *value, void *stream)
+{
+    return nt_value("r48_ntuple_value", boards, n, cells, m, L, nullptr, 0, tables, value, stream);
+}
+
+int r48_ntuple_value_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                            const uint8_t *cuts, int32_t n_cuts, const float *tables, float *value, void *stream)
+{
+    return nt_value("r48_ntuple_value_staged", boards, n, cells, m, L, cuts, n_cuts, tables, value, stream);
+}
+
+int r48_ntuple_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                   int8_t *actions, int8_t *after, float *value, int32_t *reward, uint8_t *legal, void *stream)
+{
+    return nt_act("r48_ntuple_act", boards, n, cells, m, L, nullptr, 0, tables, actions, after, value, reward, legal, stream);
+}
+
+int r48_ntuple_act_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                          const uint8_t *cuts, int32_t n_cuts, const float *tables, int8_t *actions, int8_t *after,
+                          float *value, int32_t *reward, uint8_t *legal, void *stream)
+{
+    return nt_act("r48_ntuple_act_staged", boards, n, cells, m, L, cuts, n_cuts, tables, actions, after, value, reward, legal,
+                  stream);
+}
+
+int r48_ntuple_td_act(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                      const int8_t *prev_after, const float *prev_value, const uint8_t *prev_done,
+                      const uint8_t *prev_valid, int8_t *actions, int8_t *after, float *value, int32_t *reward,
+                      uint8_t *legal, uint8_t *valid_out, float *delta_out, int64_t *acc, uint32_t *cnt, void *stream)
+{
+    return nt_td_act("r48_ntuple_td_act", boards, n, cells, m, L, nullptr, 0, tables, prev_after, prev_value, prev_done,
+                     prev_valid, actions, after, value, reward, legal, valid_out, delta_out, acc, cnt, nullptr, stream);
+}
+
+int r48_ntuple_td_act_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                             const uint8_t *cuts, int32_t n_cuts, const float *tables, const int8_t *prev_after,
+                             const float *prev_value, const uint8_t *prev_done, const uint8_t *prev_valid,
+                             int8_t *actions, int8_t *after, float *value, int32_t *reward, uint8_t *legal,
+                             uint8_t *valid_out, float *delta_out, int64_t *acc, uint32_t *cnt, uint8_t *own, void *stream)
+{
+    return nt_td_act("r48_ntuple_td_act_staged", boards, n, cells, m, L, cuts, n_cuts, tables, prev_after, prev_value,
+                     prev_done, prev_valid, actions, after, value, reward, legal, valid_out, delta_out, acc, cnt, own, stream);
+}
+
+int r48_ntuple_search(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                      int32_t depth, int8_t *actions, float *q, uint8_t *legal, void *stream)
+{
+    return nt_search("r48_ntuple_search", boards, n, cells, m, L, nullptr, 0, tables, depth, actions, q, legal, stream);
+}
+
+int r48_ntuple_search_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                             const uint8_t *cuts, int32_t n_cuts, const float *tables, int32_t depth, int8_t *actions,
+                             float *q, uint8_t *legal, void *stream)
+{
+    return nt_search("r48_ntuple_search_staged", boards, n, cells, m, L, cuts, n_cuts, tables, depth, actions, q, legal,
+                     stream);
+}
+
+int r48_ntuple_search3(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                       const float *tables, int8_t *actions, float *q, uint8_t *legal, void *stream)
+{
+    return nt_search3("r48_ntuple_search3", boards, n, cells, m, L, nullptr, 0, tables, actions, q, legal, stream);
+}
+
+int r48_ntuple_search3_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                              const uint8_t *cuts, int32_t n_cuts, const float *tables, int8_t *actions, float *q,
+                              uint8_t *legal, void *stream)
+{
+    return nt_search3("r48_ntuple_search3_staged", boards, n, cells, m, L, cuts, n_cuts, tables, actions, q, legal, stream);
+}
+
+int r48_ntuple_search_ruled(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                            const float *tables, const uint8_t *rule, int8_t *actions, float *q, uint8_t *legal,
+                            uint8_t *depth_out, void *stream)
+{
+    return nt_search_ruled("r48_ntuple_search_ruled", boards, n, cells, m, L, nullptr, 0, tables, rule, actions, q, legal,
+                           depth_out, stream);
+}
+
+int r48_ntuple_search_ruled_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                                   const uint8_t *cuts, int32_t n_cuts, const float *tables, const uint8_t *rule,
+                                   int8_t *actions, float *q, uint8_t *legal, uint8_t *depth_out, void *stream)
+{
+    return nt_search_ruled("r48_ntuple_search_ruled_staged", boards, n, cells, m, L, cuts, n_cuts, tables, rule, actions, q,
+                           legal, depth_out, stream);
+}
+
+int r48_ntuple_play(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                    int32_t depth, int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step, int32_t *length,
+                    int32_t *gain, uint8_t *done, void *stream)
+{
+    return nt_play("r48_ntuple_play", boards, n, cells, m, L, nullptr, 0, tables, depth, n_steps, env_seed, gid0, env_step,
+                   length, gain, done, stream);
+}
+
+int r48_ntuple_play_staged(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const uint8_t *cuts,
+                           int32_t n_cuts, const float *tables, int32_t depth, int32_t n_steps, uint64_t env_seed,
+                           int64_t gid0, uint32_t env_step, int32_t *length, int32_t *gain, uint8_t *done, void *stream)
+{
+    return nt_play("r48_ntuple_play_staged", boards, n, cells, m, L, cuts, n_cuts, tables, depth, n_steps, env_seed, gid0,
+                   env_step, length, gain, done, stream);
+}
+
+int r48_ntuple_play_ruled(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tables,
+                          const uint8_t *rule, int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step,
+                          int32_t *length, int32_t *gain, uint8_t *done, void *stream)
+{
+    return nt_play_ruled("r48_ntuple_play_ruled", boards, n, cells, m, L, nullptr, 0, tables, rule, n_steps, env_seed, gid0,
+                         env_step, length, gain, done, stream);
+}
+
+int r48_ntuple_play_ruled_staged(int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                                 const uint8_t *cuts, int32_t n_cuts, const float *tables, const uint8_t *rule,
+                                 int32_t n_steps, uint64_t env_seed, int64_t gid0, uint32_t env_step, int32_t *length,
+                                 int32_t *gain, uint8_t *done, void *stream)
+{
+    return nt_play_ruled("r48_ntuple_play_ruled_staged", boards, n, cells, m, L, cuts, n_cuts, tables, rule, n_steps, env_seed,
+                         gid0, env_step, length, gain, done, stream);
 }
 
 int r48_ntuple_accumulate(const int8_t *boards, int64_t n, const float *delta, const uint8_t *valid,
                           const uint8_t *cells, int32_t m, int32_t L, int64_t *acc, uint32_t *cnt, void *stream)
 {
-    r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_accumulate", boards, n, cells, m, L, lay,
-                                  {{"delta", delta, 4, true}, {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
-        return rc;
-    return run("k_nt_accumulate", n, lay.L, [&](auto len) {
-        launch(k_nt_accumulate<len()>, grid_for(n), kBlock, stream, boards, n, delta, valid, lay, words(acc), cnt);
-    });
+    return nt_accumulate("r48_ntuple_accumulate", boards, n, delta, valid, cells, m, L, nullptr, 0, acc, cnt, nullptr, stream);
+}
+
+int r48_ntuple_accumulate_staged(const int8_t *boards, int64_t n, const float *delta, const uint8_t *valid,
+                                 const uint8_t *cells, int32_t m, int32_t L, const uint8_t *cuts, int32_t n_cuts,
+                                 int64_t *acc, uint32_t *cnt, uint8_t *own, void *stream)
+{
+    return nt_accumulate("r48_ntuple_accumulate_staged", boards, n, delta, valid, cells, m, L, cuts, n_cuts, acc, cnt, own,
+                         stream);
 }
 
 int r48_ntuple_apply(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m, int32_t L,
                      float step, float *tables, int64_t *acc, uint32_t *cnt, void *stream)
 {
-    r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_apply", boards, n, cells, m, L, lay,
-                                  {{"tables", tables, 4, true}, {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
-        return rc;
-    return run("k_nt_apply", n, lay.L, [&](auto len) {
-        launch(k_nt_apply<len()>, grid_for(n), kBlock, stream, boards, n, valid, lay, step, tables, words(acc), cnt);
-    });
+    return nt_apply("r48_ntuple_apply", boards, n, valid, cells, m, L, nullptr, 0, step, tables, acc, cnt, nullptr, stream);
+}
+
+int r48_ntuple_apply_staged(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
+                            int32_t L, const uint8_t *cuts, int32_t n_cuts, float step, float *tables, int64_t *acc,
+                            uint32_t *cnt, uint8_t *own, void *stream)
+{
+    return nt_apply("r48_ntuple_apply_staged", boards, n, valid, cells, m, L, cuts, n_cuts, step, tables, acc, cnt, own,
+                    stream);
 }
 
 int r48_ntuple_apply_tc(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
                         int32_t L, float step, float *tables, float *tc_e, float *tc_a, int64_t *acc, uint32_t *cnt,
                         void *stream)
 {
-    r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_apply_tc", boards, n, cells, m, L, lay,
-                                  {{"tables", tables, 4, true}, {"tc_e", tc_e, 4, true}, {"tc_a", tc_a, 4, true},
-                                   {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
-        return rc;
-    return run("k_nt_apply_tc", n, lay.L, [&](auto len) {
-        launch(k_nt_apply_tc<len()>, grid_for(n), kBlock, stream, boards, n, valid, lay, step, tables, tc_e, tc_a,
-               words(acc), cnt);
-    });
+    return nt_apply_tc("r48_ntuple_apply_tc", boards, n, valid, cells, m, L, nullptr, 0, step, tables, tc_e, tc_a, acc, cnt,
+                       nullptr, stream);
+}
+
+int r48_ntuple_apply_tc_staged(const int8_t *boards, int64_t n, const uint8_t *valid, const uint8_t *cells, int32_t m,
+                               int32_t L, const uint8_t *cuts, int32_t n_cuts, float step, float *tables, float *tc_e,
+                               float *tc_a, int64_t *acc, uint32_t *cnt, uint8_t *own, void *stream)
+{
+    return nt_apply_tc("r48_ntuple_apply_tc_staged", boards, n, valid, cells, m, L, cuts, n_cuts, step, tables, tc_e, tc_a,
+                       acc, cnt, own, stream);
 }
 
 int r48_ntuple_tc_rate(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tc_e,
                        const float *tc_a, float *rate_out, void *stream)
 {
-    r48::NtLayout lay;
-    if (const int rc = check_args("r48_ntuple_tc_rate", boards, n, cells, m, L, lay,
-                                  {{"tc_e", tc_e, 4, true}, {"tc_a", tc_a, 4, true}, {"rate_out", rate_out, 4, true}}))
-        return rc;
-    return run("k_nt_tc_rate", n, lay.L, [&](auto len) {
-        launch(k_nt_tc_rate<len()>, grid_for(n), kBlock, stream, boards, n, lay, tc_e, tc_a, rate_out);
-    });
+    return nt_tc_rate("r48_ntuple_tc_rate", boards, n, cells, m, L, nullptr, 0, tc_e, tc_a, rate_out, stream);
+}
+
+int r48_ntuple_tc_rate_staged(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+                              const uint8_t *cuts, int32_t n_cuts, const float *tc_e, const float *tc_a, float *rate_out,
+                              void *stream)
+{
+    return nt_tc_rate("r48_ntuple_tc_rate_staged", boards, n, cells, m, L, cuts, n_cuts, tc_e, tc_a, rate_out, stream);
 }
 
 }  // extern "C"

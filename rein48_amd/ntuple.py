@@ -17,6 +17,14 @@ tc=True adds temporal-coherence (TC) learning rates (Beal & Smith; Jaskowski 201
 the running sum E of the mean deltas it was updated with and the running sum A of their absolute
 values, and its step is scaled by |E| / A -- 1 while its errors agree in sign, towards 0 once they
 are noise. No step size is annealed by hand; alpha = 1.0 is the recommended setting with it.
+
+stages=(c_1, ..., c_k) (1 to 3 strictly ascending exponents in 1..15) makes the net multi-stage with
+lazy weight promotion (Jaskowski 2016): k + 1 copies of every table, and a board is evaluated in stage
+#{j : its largest tile's exponent, clamped to 15, >= c_j} -- the stage of the afterstate being
+evaluated. An entry of a higher stage that was never updated reads as the nearest lower stage's
+current value (the update copies new values upwards until the first entry that has its own), so a
+fresh stage does not read as 0, and its first update starts from there. Opt-in; stages=() is the
+single-stage net, unchanged.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -85,6 +93,16 @@ def _outs(spec, given, n, boards):
     return tuple(_out(t, name, dtype, (n,) + tail, boards) for t, (name, dtype, tail) in zip(given, spec))
 
 
+def stage_cuts(stages):
+    """The cuts of a staged net as a tuple of ints: () or 1..3 strictly ascending exponents in 1..15."""
+    cuts = tuple(int(c) for c in stages)
+    if len(cuts) > 3:
+        raise ValueError("a net has at most 3 cuts (4 stages), got %r" % (cuts,))
+    if any(not 1 <= c <= 15 for c in cuts) or any(b <= a for a, b in zip(cuts, cuts[1:])):
+        raise ValueError("cuts are strictly ascending exponents in 1..15, got %r" % (cuts,))
+    return cuts
+
+
 def _rule(rule):
     """A rule of search_ruled as a tuple of 17 ints, each 1..4."""
     rule = tuple(int(d) for d in rule)
@@ -98,9 +116,12 @@ def _rule(rule):
 class NTupleNet:
     """The tables float32 [m, 16^L] and the update's scratch (acc int64, cnt uint32 held as int32,
     same shape; zero between calls) on one GPU. With tc, also the error sums tc_e and tc_a of the
-    temporal-coherence learning rates (float32, same shape, zero at the start: +512 MiB for "4x6")."""
+    temporal-coherence learning rates (float32, same shape, zero at the start: +512 MiB for "4x6").
+    With stages (S - 1 cuts) every one of these is [S, m, 16^L] and `own` (uint8, same shape: own[0]
+    all 1, the rest 0 at the start) records which entries of the higher stages have been updated;
+    every method then goes through the library's _staged entry points."""
 
-    def __init__(self, layout="4x6", device="cuda:0", tc=False):
+    def __init__(self, layout="4x6", device="cuda:0", tc=False, stages=()):
         self.cells = layout_cells(layout)
         self.m, self.L = len(self.cells), len(self.cells[0])
         self.device = torch.device(device)
@@ -108,23 +129,49 @@ class NTupleNet:
             raise ValueError("NTupleNet device must be a GPU, got %s" % self.device)
         flat = [c for t in self.cells for c in t]
         self._cells = (C.c_uint8 * len(flat))(*flat)
-        size = 16 ** self.L
-        self.tables = torch.zeros((self.m, size), dtype=torch.float32, device=self.device)
-        self.acc = torch.zeros((self.m, size), dtype=torch.int64, device=self.device)
-        self.cnt = torch.zeros((self.m, size), dtype=torch.int32, device=self.device)
+        self.cuts = stage_cuts(stages)
+        self.S = len(self.cuts) + 1
+        self._cuts = (C.c_uint8 * len(self.cuts))(*self.cuts)
+        shape = (self.S, self.m, 16 ** self.L) if self.cuts else (self.m, 16 ** self.L)
+        self.tables = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.acc = torch.zeros(shape, dtype=torch.int64, device=self.device)
+        self.cnt = torch.zeros(shape, dtype=torch.int32, device=self.device)
         self.tc = bool(tc)
-        self.tc_e = torch.zeros((self.m, size), dtype=torch.float32, device=self.device) if self.tc else None
-        self.tc_a = torch.zeros((self.m, size), dtype=torch.float32, device=self.device) if self.tc else None
+        self.tc_e = torch.zeros(shape, dtype=torch.float32, device=self.device) if self.tc else None
+        self.tc_a = torch.zeros(shape, dtype=torch.float32, device=self.device) if self.tc else None
+        self.own = None
+        if self.cuts:
+            self.own = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+            self.own[0] = 1
         self._lib = _lib.load()
 
+    def _fn(self, name):
+        """The entry point `name`, or its _staged twin on a staged net."""
+        return getattr(self._lib, name + "_staged" if self.cuts else name)
+
     def _lay(self):
+        """What every entry point takes from cells on: (cells, m, L), and the cuts on a staged net."""
+        if self.cuts:
+            return self._cells, self.m, self.L, self._cuts, len(self.cuts)
         return self._cells, self.m, self.L
+
+    def _own(self):
+        """The trailing own argument of the updating entry points' staged twins."""
+        return (ptr(self.own),) if self.cuts else ()
+
+    def stage(self, boards):
+        """uint8 [n]: the stage each board is evaluated in (0 on an unstaged net)."""
+        top = boards.reshape(-1, 16).clamp(max=15).max(dim=1).values
+        out = torch.zeros(top.shape, dtype=torch.uint8, device=boards.device)
+        for c in self.cuts:
+            out += (top >= c).to(torch.uint8)
+        return out
 
     def value(self, boards, out=None):
         """float32 [n]: V of int8 boards [..., 16]."""
         n = _boards(boards)
         out = _out(out, "out", torch.float32, (n,), boards)
-        check(self._lib.r48_ntuple_value(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(out), _stream(boards)))
+        check(self._fn("r48_ntuple_value")(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(out), _stream(boards)))
         return out
 
     def act(self, boards, actions=None, after=None, value=None, reward=None, legal=None):
@@ -134,7 +181,7 @@ class NTupleNet:
         value 0, reward 0, legal 0."""
         n = _boards(boards)
         outs = _outs(_ACT_OUT, (actions, after, value, reward, legal), n, boards)
-        check(self._lib.r48_ntuple_act(ptr(boards), n, *self._lay(), ptr(self.tables), *map(ptr, outs), _stream(boards)))
+        check(self._fn("r48_ntuple_act")(ptr(boards), n, *self._lay(), ptr(self.tables), *map(ptr, outs), _stream(boards)))
         return outs
 
     def td_act(self, boards, prev_after, prev_value, prev_done, prev_valid, actions=None, after=None, value=None,
@@ -153,9 +200,9 @@ class NTupleNet:
             if _dev(t, name, dtype).numel() != n:
                 raise ValueError("%s must have one element per board (%d)" % (name, n))
         outs = _outs(_TD_ACT_OUT, (actions, after, value, reward, legal, valid, delta), n, boards)
-        check(self._lib.r48_ntuple_td_act(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(prev_after),
+        check(self._fn("r48_ntuple_td_act")(ptr(boards), n, *self._lay(), ptr(self.tables), ptr(prev_after),
                                           ptr(prev_value), ptr(prev_done), ptr(prev_valid), *map(ptr, outs),
-                                          ptr(self.acc), ptr(self.cnt), _stream(boards)))
+                                          ptr(self.acc), ptr(self.cnt), *self._own(), _stream(boards)))
         return outs
 
     def accumulate(self, boards, delta, valid=None):
@@ -164,8 +211,8 @@ class NTupleNet:
         _dev(delta, "delta", torch.float32)
         if delta.numel() != n or (valid is not None and _dev(valid, "valid", torch.uint8).numel() != n):
             raise ValueError("delta / valid must have one element per board (%d)" % n)
-        check(self._lib.r48_ntuple_accumulate(ptr(boards), n, ptr(delta), ptr(valid), *self._lay(), ptr(self.acc),
-                                              ptr(self.cnt), _stream(boards)))
+        check(self._fn("r48_ntuple_accumulate")(ptr(boards), n, ptr(delta), ptr(valid), *self._lay(), ptr(self.acc),
+                                                      ptr(self.cnt), *self._own(), _stream(boards)))
 
     def apply(self, boards, step, valid=None):
         """Second half: every entry the boards hit moves by step * its mean delta (a TC net: times
@@ -174,12 +221,12 @@ class NTupleNet:
         if valid is not None and _dev(valid, "valid", torch.uint8).numel() != n:
             raise ValueError("valid must have one element per board (%d)" % n)
         if self.tc:
-            check(self._lib.r48_ntuple_apply_tc(ptr(boards), n, ptr(valid), *self._lay(), float(step),
+            check(self._fn("r48_ntuple_apply_tc")(ptr(boards), n, ptr(valid), *self._lay(), float(step),
                                                 ptr(self.tables), ptr(self.tc_e), ptr(self.tc_a), ptr(self.acc),
-                                                ptr(self.cnt), _stream(boards)))
+                                                        ptr(self.cnt), *self._own(), _stream(boards)))
             return
-        check(self._lib.r48_ntuple_apply(ptr(boards), n, ptr(valid), *self._lay(), float(step), ptr(self.tables),
-                                         ptr(self.acc), ptr(self.cnt), _stream(boards)))
+        check(self._fn("r48_ntuple_apply")(ptr(boards), n, ptr(valid), *self._lay(), float(step), ptr(self.tables),
+                                                 ptr(self.acc), ptr(self.cnt), *self._own(), _stream(boards)))
 
     def td_update(self, afterstates, delta, alpha, valid=None):
         """tables[e] += alpha / (8m) * mean over the valid boards hitting e of delta, for every entry
@@ -195,7 +242,7 @@ class NTupleNet:
             raise ValueError("tc_rate needs a net built with tc=True")
         n = _boards(boards)
         out = _out(out, "out", torch.float32, (n,), boards)
-        check(self._lib.r48_ntuple_tc_rate(ptr(boards), n, *self._lay(), ptr(self.tc_e), ptr(self.tc_a), ptr(out),
+        check(self._fn("r48_ntuple_tc_rate")(ptr(boards), n, *self._lay(), ptr(self.tc_e), ptr(self.tc_a), ptr(out),
                                            _stream(boards)))
         return out
 
@@ -209,7 +256,7 @@ class NTupleNet:
             raise ValueError("search depth is 1 or 2, got %r (three plies: search3)" % (depth,))
         n = _boards(boards)
         outs = _outs(_SEARCH_OUT, (actions, q, legal), n, boards)
-        check(self._lib.r48_ntuple_search(ptr(boards), n, *self._lay(), ptr(self.tables), depth, *map(ptr, outs),
+        check(self._fn("r48_ntuple_search")(ptr(boards), n, *self._lay(), ptr(self.tables), depth, *map(ptr, outs),
                                           _stream(boards)))
         return outs
 
@@ -222,7 +269,7 @@ class NTupleNet:
         children."""
         n = _boards(boards)
         outs = _outs(_SEARCH_OUT, (actions, q, legal), n, boards)
-        check(self._lib.r48_ntuple_search3(ptr(boards), n, *self._lay(), ptr(self.tables), *map(ptr, outs),
+        check(self._fn("r48_ntuple_search3")(ptr(boards), n, *self._lay(), ptr(self.tables), *map(ptr, outs),
                                            _stream(boards)))
         return outs
 
@@ -257,7 +304,7 @@ class NTupleNet:
         rule = _rule(rule)
         n = _boards(boards)
         outs = _outs(_RULED_OUT, (actions, q, legal, depth), n, boards)
-        check(self._lib.r48_ntuple_search_ruled(ptr(boards), n, *self._lay(), ptr(self.tables), (C.c_uint8 * 17)(*rule),
+        check(self._fn("r48_ntuple_search_ruled")(ptr(boards), n, *self._lay(), ptr(self.tables), (C.c_uint8 * 17)(*rule),
                                                 *map(ptr, outs), _stream(boards)))
         return outs
 
@@ -303,7 +350,7 @@ class NTupleNet:
         n_steps = int(n_steps)
         length, gain, done = self._play_outs(n, boards, length, gain, done)
         step, reset = env.counters
-        check(self._lib.r48_ntuple_play(ptr(boards), n, *self._lay(), ptr(self.tables), depth, n_steps, env.seed,
+        check(self._fn("r48_ntuple_play")(ptr(boards), n, *self._lay(), ptr(self.tables), depth, n_steps, env.seed,
                                         env.board_offset, step, ptr(length), ptr(gain), ptr(done), _stream(boards)))
         env.counters = ((step + n_steps) & 0xFFFFFFFF, reset)
         return boards, length, gain, done
@@ -327,7 +374,7 @@ class NTupleNet:
         n_steps = int(n_steps)
         length, gain, done = self._play_outs(n, boards, length, gain, done)
         step, reset = env.counters
-        check(self._lib.r48_ntuple_play_ruled(ptr(boards), n, *self._lay(), ptr(self.tables), (C.c_uint8 * 17)(*rule),
+        check(self._fn("r48_ntuple_play_ruled")(ptr(boards), n, *self._lay(), ptr(self.tables), (C.c_uint8 * 17)(*rule),
                                               n_steps, env.seed, env.board_offset, step, ptr(length), ptr(gain),
                                               ptr(done), _stream(boards)))
         env.counters = ((step + n_steps) & 0xFFFFFFFF, reset)
@@ -390,6 +437,8 @@ class NTupleNet:
 
     def state_dict(self):
         st = {"cells": [list(t) for t in self.cells], "tables": self.tables.detach().to("cpu", copy=True)}
+        if self.cuts:
+            st.update(stages=list(self.cuts), own=self.own.detach().to("cpu", copy=True))
         if self.tc:
             st.update(tc_e=self.tc_e.detach().to("cpu", copy=True), tc_a=self.tc_a.detach().to("cpu", copy=True))
         return st
@@ -397,9 +446,13 @@ class NTupleNet:
     def load_state_dict(self, st):
         if [list(t) for t in self.cells] != [list(t) for t in st["cells"]]:
             raise ValueError("NTupleNet: the layout is %r, the saved one %r" % (self.cells, st["cells"]))
+        if self.cuts != tuple(st.get("stages", ())):   # a state without the key is an unstaged net's
+            raise ValueError("NTupleNet: the stages are %r, the saved ones %r" % (self.cuts, tuple(st.get("stages", ()))))
         if self.tc and not ("tc_e" in st and "tc_a" in st):
             raise ValueError("NTupleNet: a tc=True net needs the saved tc_e / tc_a, the state has none")
         self.tables.copy_(st["tables"].to(self.device))
+        if self.cuts:
+            self.own.copy_(st["own"].to(self.device))
         if self.tc:
             self.tc_e.copy_(st["tc_e"].to(self.device))
             self.tc_a.copy_(st["tc_a"].to(self.device))
@@ -419,6 +472,7 @@ class NTupleConfig:
     seed: int = 0
     tc: bool = False                 # temporal-coherence learning rates; alpha = 1.0 is recommended with it
     fused: bool = False              # train_step in three launches (td_act, apply, env.step): the same bits
+    stages: tuple = ()               # cuts of a multi-stage net with weight promotion: () or 1..3 ascending exponents in 1..15
 
 
 class NTupleTrainer:
@@ -441,7 +495,7 @@ class NTupleTrainer:
         self.device = torch.device(device)
         self.rank = 0
         n = cfg.n_boards
-        self.net = NTupleNet(cfg.layout, self.device, tc=cfg.tc)
+        self.net = NTupleNet(cfg.layout, self.device, tc=cfg.tc, stages=cfg.stages)
         self.env = VecGame(n, device=self.device, seed=cfg.seed)
         self.device = self.env.device
         self.env.reset()

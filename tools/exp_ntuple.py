@@ -101,6 +101,14 @@ evaluations of (a) also with 64 and 512 episodes. Writes exp_ntuple_play_ruled.j
 board on whole evaluations: --episodes episodes to the end in play_episodes' chunks through each --ab-lib
 build, and single launches and whole evaluations of 64 boards, where one board's latency is what counts.
 Writes exp_ntuple_play_ruled_waves.json.
+
+With --stages, multi-stage tables with weight promotion: (a) value, act, search depth 2, search3, accumulate +
+apply, accumulate + apply_tc and the TC trainer's fused and unfused step with stages=(9,) against the unstaged
+net on the same boards, --sizes boards (default 4096,65536), the two builds' windows interleaved; (b) with
+--scores, the 4x6 TC recipe (4,096 boards, alpha 1.0, seed 0, fused) for --budgets steps (default 10000,40000)
+with the cuts (), (9,), (10,) and (8, 10): --episodes whole games at eval seed 13 at depths 1, 2 and 3, the share
+of games reaching 2,048 / 4,096 / 8,192 and the share of own[1] set. --no-kernels skips (a). Writes
+exp_ntuple_stages.json.
 """
 import argparse
 import json
@@ -1274,6 +1282,116 @@ def main_play_ruled(args):
         torch.cuda.empty_cache()
 
 
+def stage_kernels(layout, n, cuts):
+    """value, act, search depth 2, search3 and the two update pairs on the same running boards, staged
+    against unstaged, their windows interleaved."""
+    nets = {"plain": NTupleNet(layout, device=DEV, tc=True), "staged": NTupleNet(layout, device=DEV, tc=True, stages=cuts)}
+    g = torch.Generator(device=DEV).manual_seed(1)
+    nets["plain"].tables.copy_(torch.randn(nets["plain"].tables.shape, generator=g, device=DEV) * 30.0)
+    nets["staged"].tables[:] = nets["plain"].tables               # every stage alike: both play the same moves
+    boards = running_boards(n)
+    after = nets["plain"].act(boards)[1]
+    delta = torch.randn(n, generator=g, device=DEV) * 100.0
+    res = {"layout": layout, "boards": n, "cuts": list(cuts),
+           "share_of_boards_above_stage_0": float((nets["staged"].stage(after) > 0).float().mean())}
+    value = torch.empty(n, device=DEV)
+    fns = {}
+    for k, net in nets.items():
+        fns["value_" + k] = lambda net=net: net.value(after, out=value)
+        fns["act_" + k] = lambda net=net: net.act(boards)
+        fns["search2_" + k] = lambda net=net: net.search(boards, 2)
+        fns["search3_" + k] = lambda net=net: net.search3(boards)
+    t = alternated_ms(fns, calls=5 if n > 8192 else 20)
+    for name in ("value", "act", "search2", "search3"):
+        res[name] = {"plain": _ms(t[name + "_plain"]), "staged": _ms(t[name + "_staged"]),
+                     "staged_over_plain": t[name + "_staged"][0] / t[name + "_plain"][0]}
+
+    def update(net, tc):
+        def fn():
+            net.tc = tc                                           # the same arrays through apply or apply_tc
+            net.td_update(after, delta, 1.0 if tc else 0.25)
+        return fn
+    t = alternated_ms({"%s_%s" % (name, k): update(net, tc) for name, tc in (("accumulate_apply", False),
+                                                                              ("accumulate_apply_tc", True))
+                       for k, net in nets.items()})
+    for name in ("accumulate_apply", "accumulate_apply_tc"):
+        res[name] = {"plain": _ms(t[name + "_plain"]), "staged": _ms(t[name + "_staged"]),
+                     "staged_over_plain": t[name + "_staged"][0] / t[name + "_plain"][0]}
+    del nets
+    torch.cuda.empty_cache()
+    return res
+
+
+def stage_train_step(layout, n, cuts):
+    """The TC trainer's step (alpha 1.0), fused and unfused, staged against unstaged, windows interleaved."""
+    trs = {"%s_%s" % (f, k): NTupleTrainer(NTupleConfig(n_boards=n, layout=layout, alpha=1.0, seed=3, tc=True,
+                                                         fused=f == "fused", stages=st), device=DEV)
+           for f in ("unfused", "fused") for k, st in (("plain", ()), ("staged", cuts))}
+    t = alternated_ms({k: tr.train_step for k, tr in trs.items()}, warmup=20)
+    res = {"layout": layout, "boards": n, "cuts": list(cuts)}
+    for f in ("unfused", "fused"):
+        res["train_step_" + f] = {"plain": _ms(t[f + "_plain"]), "staged": _ms(t[f + "_staged"]),
+                                  "staged_over_plain": t[f + "_staged"][0] / t[f + "_plain"][0]}
+    del trs
+    torch.cuda.empty_cache()
+    return res
+
+
+def stage_scores(layout, n_boards, steps, cuts, eval_seed=13, episodes=4096, depths=(1, 2, 3)):
+    """One budget of the fused TC trainer (alpha 1.0, seed 0) with the given cuts, then whole episodes at
+    each depth: mean, standard error, the share of games whose largest tile reaches 2,048 / 4,096 /
+    8,192, and the share of own[1] set."""
+    tr = NTupleTrainer(NTupleConfig(n_boards=n_boards, layout=layout, alpha=1.0, seed=0, tc=True, fused=True, stages=cuts),
+                       device=DEV)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tr.train_steps(steps)
+    torch.cuda.synchronize()
+    row = {"layout": layout, "cuts": list(cuts), "train_boards": n_boards, "train_steps": steps, "eval_seed": eval_seed,
+           "episodes": episodes, "train_seconds": time.perf_counter() - t0}
+    if cuts:
+        row["share_of_own_1_set"] = float(tr.net.own[1].float().mean())
+        row["share_of_train_boards_above_stage_0"] = float((tr.net.stage(tr.env.boards) > 0).float().mean())
+    for depth in depths:
+        t0 = time.perf_counter()
+        ev = tr.net.play_episodes(episodes, seed=eval_seed, depth=depth, return_scores=True)
+        sc = ev.pop("scores").numpy()
+        ev["score_std"] = float(sc.std(ddof=1))
+        ev["standard_error"] = ev["score_std"] / episodes ** 0.5
+        hist = ev["max_tile_exponent_hist"]
+        for e in (11, 12, 13):
+            ev["reach_%d" % (1 << e)] = sum(f for k, f in hist.items() if k >= e)
+        ev["eval_seconds"] = time.perf_counter() - t0
+        row["depth%d" % depth] = ev
+    del tr
+    torch.cuda.empty_cache()
+    return row
+
+
+def main_stages(args):
+    """--stages: what multi-stage tables cost (stages=(9,) against unstaged, --sizes boards, default
+    4096,65536) and, with --scores, what they score: 4x6 TC at 4,096 boards for --budgets train steps
+    (default 10000,40000) with the cuts (), (9,), (10,) and (8, 10). Writes exp_ntuple_stages.json."""
+    out = {"device": torch.cuda.get_device_name(0), "kernels": [], "train_step": [], "scores": []}
+    if not args.no_kernels:
+        for layout in ("lines-squares", "4x6"):
+            for n in (int(s) for s in (args.sizes or "4096,65536").split(",")):
+                for fn in (stage_kernels, stage_train_step):
+                    r = fn(layout, n, (9,))
+                    out["kernels" if fn is stage_kernels else "train_step"].append(r)
+                    print(json.dumps(r), flush=True)
+    if args.scores:
+        for steps in (int(s) for s in args.budgets.split(",")):
+            for cuts in ((), (9,), (10,), (8, 10)):
+                r = stage_scores("4x6", 4096, steps, cuts, episodes=args.episodes)
+                out["scores"].append(r)
+                print(json.dumps(r), flush=True)
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        with open(os.path.join(args.out, "exp_ntuple_stages.json"), "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main_search(args):
     out = {"device": torch.cuda.get_device_name(0), "kernels": [], "scores": []}
     for layout in ("lines-squares", "4x6"):
@@ -1311,9 +1429,14 @@ def main():
     ap.add_argument("--play-ruled", action="store_true")
     ap.add_argument("--no-episodes", action="store_true")
     ap.add_argument("--waves-ab", action="store_true")
+    ap.add_argument("--stages", action="store_true")
+    ap.add_argument("--budgets", default="10000,40000")
+    ap.add_argument("--no-kernels", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("exp_ntuple.py needs a GPU")
+    if args.stages:
+        return main_stages(args)
     if args.play_ruled:
         return main_play_ruled(args)
     if args.ruled:
