@@ -841,6 +841,32 @@ int r48_ntuple_tc_rate_staged(const int8_t *boards, int64_t n, const uint8_t *ce
                               const uint8_t *cuts, int32_t n_cuts, const float *tc_e, const float *tc_a,
                               float *rate_out, void *stream);
 
+/* ---- Carousel shaping (Jaskowski 2016): episodes start in turn from stage 0, 1, ..., S - 1, from a
+ * board with which a recent episode entered that stage. Call it after r48_env_step with
+ * R48_AUTO_RESET, on the env's boards in place, with that step's done. cuts (uint8, n_cuts in 1..3,
+ * strictly ascending exponents in 1..15) are the carousel's own: S = n_cuts + 1, the stage of a
+ * board is that of the _staged entry points, taken from the env board. They need not be a net's.
+ * Caller-owned state, all zero before the first call:
+ *   pool     int8  [S - 1][n][16]  pool[s - 1][i]: the board with which slot i last entered stage s
+ *   pool_has uint8 [S - 1][n]      1 where the pool slot holds a board
+ *   seen     uint8 [n]             highest stage slot i's episode was recorded or started in
+ *   turn     uint8 [n]             stage of slot i's last episode start
+ *   starts   uint64 [S], nullable  episode starts per stage (+=)
+ * Restart phase, boards with done[i] != 0: t = (turn[i] + 1) % S; where t > 0 the donor is
+ * j = mulhi(w0, (uint32)n), w0 = word 0 of Philox4x32-10(key = seed, counter = {gid lo, gid hi, ctr,
+ * 0xCA70}), gid = gid0 + i, and boards[i] = pool[t - 1][j] where pool_has[t - 1][j], else t = 0 and
+ * the fresh board stays; then turn[i] = t, seen[i] = stage(boards[i]), starts[t] += 1. It reads the
+ * pool as it was before the call. Record phase, boards with done[i] == 0: s = stage(boards[i]);
+ * where s > seen[i], pool[s - 1][i] = boards[i], pool_has[s - 1][i] = 1, seen[i] = s. Two launches
+ * on the stream, restart then record; bitwise reproducible, independent of the launch geometry; the
+ * result depends on the batch through n and gid0. boards and pool must not overlap.
+ * R48_EINVAL (before any HIP call) for NULL boards, done, cuts, pool, pool_has, seen or turn, boards
+ * or pool not 16-byte aligned, starts not 8-byte aligned, n < 0 or n > 2^31 - 1, n_cuts outside
+ * 1..3, a cut outside 1..15 and cuts not strictly ascending. n == 0 is a no-op after these checks. */
+int r48_ntuple_carousel(int8_t *boards, int64_t n, const uint8_t *done, const uint8_t *cuts, int32_t n_cuts,
+                        int8_t *pool, uint8_t *pool_has, uint8_t *seen, uint8_t *turn,
+                        uint64_t *starts /* nullable */, uint64_t seed, int64_t gid0, uint32_t ctr, void *stream);
+
 /* Thread-local message of the last failed call on this thread ("" if none). */
 const char *r48_last_error(void);
 /* "rein48 <version> gfx950" */

@@ -11,7 +11,8 @@ is bit-identical to training that never stopped (tests/test_checkpoint_gpu.py):
               slot order: 38 B per stored transition)
   NTupleTrainer  the tables (with cfg.tc also the error sums tc_e / tc_a, with cfg.stages also the cuts and the own flags), the env's boards and counters, the previous step's afterstates, values,
               done and valid flags, and the step count (the update is deterministic: integer
-              atomics, one plain table update per entry)
+              atomics, one plain table update per entry); with cfg.carousel also its cuts and its
+              five buffers (pool, pool_has, seen, turn, starts)
 Draws are keyed by counters, not by RNG state in memory, so restoring the
 counters restores every later draw.
 
@@ -129,6 +130,9 @@ def save(trainer, path, replay=True):
             st.update(tc_e=_cpu(trainer.net.tc_e), tc_a=_cpu(trainer.net.tc_a))
         if trainer.net.cuts:
             st.update(cfg=dict(cfg, stages=list(trainer.net.cuts)), stages=list(trainer.net.cuts), own=_cpu(trainer.net.own))
+        if trainer.carousel:
+            st.update(cfg=dict(st["cfg"], carousel=list(trainer.carousel)), carousel=list(trainer.carousel),
+                      carousel_state={k: _cpu(getattr(trainer, k)) for k in trainer.CAROUSEL_STATE})
     elif kind == "a3c":
         st.update(net=_cpu_state(trainer.net), ms=_cpu(trainer.opt.ms), mom=_cpu(trainer.opt.mom),
                   env=_env_state(trainer.env), sample_ctr=int(trainer.sample_ctr))
@@ -174,9 +178,14 @@ def load(trainer, path):
     # the cuts of a staged net, compared as cuts like the cells; a file without the key is an unstaged trainer's
     if kind == "ntuple" and tuple(st.get("stages", ())) != trainer.net.cuts:
         raise ValueError("checkpoint: stages %r in the trainer, %r in %s" % (trainer.net.cuts, tuple(st.get("stages", ())), path))
+    # the carousel's cuts likewise; a file without the key is a trainer's without carousel
+    if kind == "ntuple" and tuple(st.get("carousel", ())) != trainer.carousel:
+        raise ValueError("checkpoint: carousel %r in the trainer, %r in %s" % (trainer.carousel, tuple(st.get("carousel", ())), path))
     dev = trainer.device
     with torch.no_grad():
         if kind == "ntuple":
+            for k in trainer.CAROUSEL_STATE if trainer.carousel else ():
+                getattr(trainer, k).copy_(st["carousel_state"][k].to(dev))
             trainer.net.tables.copy_(st["tables"].to(dev))
             if trainer.net.cuts:
                 trainer.net.own.copy_(st["own"].to(dev))

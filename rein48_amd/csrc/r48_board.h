@@ -458,6 +458,9 @@ static constexpr uint32_t kStepTag = 0x2048u;
 static constexpr int kStepRounds = 7;
 static constexpr uint32_t kResetTag = 0x5E7u;
 static constexpr uint32_t kFillTag = 0xF111u;   // synthetic start boards (r48_env_fill_random)
+// the donor draw of carousel shaping (r48_ntuple.h, r48_ntuple_carousel); the other tags in use are
+// kSampleTag 0xA3C, kEgreedyTag 0xD0E (r48_select.h), kPermTag 0x5A3 and kRingTag 0x5A4 (r48_replay.hip)
+static constexpr uint32_t kCarouselTag = 0xCA70u;
 static constexpr uint32_t kFourThresh = 0x1999999Au;     // P(4) = 0.1   (GameClient.py:125)
 static constexpr uint32_t kFourThresh30 = 0x06666666u;   // same on 30 bits (P = 0.1 - 4e-10)
 static constexpr uint32_t kFourThresh28 = 0x0199999Au;   // same on 28 bits

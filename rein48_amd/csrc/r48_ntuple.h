@@ -94,10 +94,43 @@
 // entry offset is the constant 0 and nothing is computed) or NtCuts (the cuts in one word).
 // nt_staged_update_pull restates the update on the host in the PULL form: an unowned entry is not
 // stored at all, a read resolves to the nearest lower owned stage and a first touch copies it.
+//
+// Carousel shaping (Jaskowski 2016; k_nt_carousel_restart + k_nt_carousel_record, nt_carousel_host
+// on the host). Episodes start in turn from stage 0, 1, ..., S - 1, from a board with which a recent
+// episode ENTERED that stage, so every stage gets an equal share of the episode starts. The carousel
+// has its own cuts (1..3, checked as the stage cuts are; they need not be the net's, and the net may
+// be unstaged), S = n_cuts + 1, and the stage of a board is nt_stage(cuts, board) of the ENV board,
+// after the spawn. Per board slot i of a batch of n, all caller-owned:
+//     pool     int8  [S - 1][n][16]  pool[s - 1][i]: the board with which slot i last entered stage s
+//     pool_has uint8 [S - 1][n]      1 where the pool slot holds a board            (0 at the start)
+//     seen     uint8 [n]             highest stage the slot's current episode was recorded or
+//                                    started in                                     (0 at the start)
+//     turn     uint8 [n]             stage of the slot's last episode start         (0 at the start)
+//     starts   uint64 [S], nullable  episode starts per stage                       (0 at the start)
+// One call follows an env step with auto-reset and works on the boards in place, with that step's
+// done flags, in two phases over the whole batch, in this order:
+//   RESTART, boards with done[i] != 0 (the env has put a fresh board there):
+//     t = (turn[i] + 1) % S
+//     t > 0: the donor is j = mulhi(w0, (uint32)n), w0 = word 0 of Philox4x32-10(key = {seed lo,
+//            seed hi}, counter = {gid lo, gid hi, ctr, kCarouselTag}), gid = gid0 + i. Where
+//            pool_has[t - 1][j], boards[i] = pool[t - 1][j]; else t = 0 (the paper's fallback to the
+//            first stage) -- the next restart of the slot tries stage 1 again
+//     t == 0: the fresh board stays
+//     then turn[i] = t, seen[i] = nt_stage(cuts, boards[i]), starts[t] += 1
+//   RECORD, boards with done[i] == 0:
+//     s = nt_stage(cuts, boards[i]); where s > seen[i]: pool[s - 1][i] = boards[i],
+//     pool_has[s - 1][i] = 1, seen[i] = s
+// The restart phase reads the pool as it was BEFORE the call: a donor slot may record in the same
+// call, so on the GPU the phases are two launches on one stream, restart then record (one kernel
+// would race; no grid-wide barrier). Every slot writes its own pool slot only, there is no shared
+// ring: plain stores of integers, and integer atomics (order-free) for starts. The result is bitwise
+// reproducible and independent of the launch geometry; it depends on the batch through n and gid0.
 #pragma once
 #include <stdint.h>
 
 #if !defined(__HIP_DEVICE_COMPILE__)
+#include <string.h>
+
 #include <map>
 #include <vector>
 #endif
@@ -253,6 +286,68 @@ R48_HD uint32_t nt_base(const NtCuts &c, int32_t m, const Board &b)
 {
     return (nt_stage(c, b) * (uint32_t)m) << (4 * L);
 }
+
+// ---- carousel shaping --------------------------------------------------------------------------
+// NULL, or what is wrong with a carousel's cuts: the stage cuts' rules, and at least one cut
+inline const char *nt_carousel_cuts_check(const uint8_t *cuts, int n_cuts)
+{
+    if (n_cuts < 1 || n_cuts > kNtMaxCuts)
+        return "n_cuts must be 1..3";
+    return nt_cuts_check(cuts, n_cuts);
+}
+
+// t of the contract before the pool is looked at: the stage after the slot's last start, S - 1 wraps to 0
+R48_HD uint32_t nt_carousel_turn(uint32_t turn, const NtCuts &c) { return (turn + 1u) % (uint32_t)(c.n + 1); }
+
+// the donor slot j of restarting board gid: one Philox4x32-10 block, word 0 scaled to 0..n - 1
+R48_HD uint32_t nt_carousel_donor(uint64_t gid, uint32_t ctr, uint32_t k0, uint32_t k1, uint32_t n)
+{
+    uint32_t w[4] = {(uint32_t)gid, (uint32_t)(gid >> 32), ctr, kCarouselTag};
+    philox4x32_10(w, k0, k1);
+    return mulhi(w[0], n);
+}
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// One call of the contract on the host, serially: the restart phase over the whole batch, then the
+// record phase. The restart phase writes no pool slot, so it reads the pool as it was before the call.
+inline void nt_carousel_host(int8_t *boards, int64_t n, const uint8_t *done, const NtCuts &cuts, int8_t *pool,
+                             uint8_t *pool_has, uint8_t *seen, uint8_t *turn, uint64_t *starts, uint64_t seed,
+                             int64_t gid0, uint32_t ctr)
+{
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int64_t i = 0; i < n; i++) {
+        if (!done[i])
+            continue;
+        uint32_t t = nt_carousel_turn(turn[i], cuts);
+        if (t > 0u) {
+            const int64_t at = (int64_t)(t - 1u) * n + nt_carousel_donor((uint64_t)(gid0 + i), ctr, k0, k1, (uint32_t)n);
+            if (pool_has[at])
+                memcpy(boards + 16 * i, pool + 16 * at, 16);
+            else
+                t = 0u;
+        }
+        Board b;
+        memcpy(&b, boards + 16 * i, 16);
+        turn[i] = (uint8_t)t;
+        seen[i] = (uint8_t)nt_stage(cuts, b);
+        if (starts)
+            starts[t] += 1u;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        if (done[i])
+            continue;
+        Board b;
+        memcpy(&b, boards + 16 * i, 16);
+        const uint32_t s = nt_stage(cuts, b);
+        if (s > seen[i]) {
+            const int64_t at = (int64_t)(s - 1u) * n + i;
+            memcpy(pool + 16 * at, boards + 16 * i, 16);
+            pool_has[at] = 1;
+            seen[i] = (uint8_t)s;
+        }
+    }
+}
+#endif
 
 // entry index of one placed tuple
 template <int L>

@@ -25,6 +25,8 @@
 //                                                                k_nt_play2 (over nt_wave_q2),
 //                                                                k_nt_play_ruled (over the ruled search)
 // and r48_ntuple.h's nt_value (k_nt_value and everything above) and nt_tc_rate_mean (k_nt_tc_rate).
+// k_nt_carousel_restart and k_nt_carousel_record are the two phases of carousel shaping
+// (r48_ntuple.h), over nt_stage, nt_carousel_turn and nt_carousel_donor.
 // k_nt_td_act is act, the trainer's TD error and accumulate for the previous step's afterstates in
 // one launch: the fused training step. k_nt_search runs one board per WAVE, k_nt_search3,
 // k_nt_search_ruled and k_nt_play_ruled one per WORKGROUP; every other kernel one board per lane
@@ -1072,6 +1074,70 @@ __global__ __launch_bounds__(64 * WAVES) void k_nt_play_ruled(int8_t *__restrict
         nt_play_store(boards, i, b, len, gn, length, gain, done);
 }
 
+// ---- carousel shaping: where the next episode of a finished board starts --------------------------
+// The carousel contract of r48_ntuple.h, one board per lane: the board and a pool slot are one
+// 16-byte load or store each, the flags bytes, the cuts wave-uniform arguments; no LDS. Two kernels,
+// launched one after the other on the stream: a restarting board may draw a donor slot whose own
+// board records in the same call, and it must read what that slot held before the call.
+
+__device__ __forceinline__ void store_board(int8_t *__restrict__ boards, int64_t i, const r48::Board &b)
+{
+    *reinterpret_cast<uint4 *>(boards + 16 * i) = make_uint4(b.w0, b.w1, b.w2, b.w3);
+}
+
+// Restart phase: the lanes of finished boards only (the others leave at once, and only these make
+// the Philox draw). Reads the pool, writes boards[i], turn[i], seen[i] and counts the start.
+__global__ __launch_bounds__(kBlock) void k_nt_carousel_restart(int8_t *__restrict__ boards, int64_t n,
+                                                                const uint8_t *__restrict__ done, const r48::NtCuts cuts,
+                                                                const int8_t *__restrict__ pool,
+                                                                const uint8_t *__restrict__ pool_has,
+                                                                uint8_t *__restrict__ seen, uint8_t *__restrict__ turn,
+                                                                unsigned long long *__restrict__ starts, uint32_t k0,
+                                                                uint32_t k1, int64_t gid0, uint32_t ctr)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || done[i] == 0)
+        return;
+    uint32_t t = r48::nt_carousel_turn(turn[i], cuts);   // 0 .. cuts.n
+    r48::Board b;
+    if (t > 0u) {
+        // j < n: mulhi of a 32-bit word with n <= 2^31 - 1, so at < cuts.n * n, the pool's slots
+        const int64_t at = (int64_t)(t - 1u) * n + r48::nt_carousel_donor((uint64_t)(gid0 + i), ctr, k0, k1, (uint32_t)n);
+        if (pool_has[at] != 0) {
+            b = r48::load_board(pool, at);
+            store_board(boards, i, b);
+        } else {
+            t = 0u;
+        }
+    }
+    if (t == 0u)
+        b = r48::load_board(boards, i);   // the env's fresh board stays
+    turn[i] = (uint8_t)t;
+    seen[i] = (uint8_t)r48::nt_stage(cuts, b);
+    if (starts)
+        atomicAdd(starts + t, 1ull);
+}
+
+// Record phase: a running board that has crossed a cut since its episode was last recorded or started
+// goes into its own pool slot of the stage it entered.
+__global__ __launch_bounds__(kBlock) void k_nt_carousel_record(const int8_t *__restrict__ boards, int64_t n,
+                                                               const uint8_t *__restrict__ done, const r48::NtCuts cuts,
+                                                               int8_t *__restrict__ pool, uint8_t *__restrict__ pool_has,
+                                                               uint8_t *__restrict__ seen)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || done[i] != 0)
+        return;
+    const r48::Board b = r48::load_board(boards, i);
+    const uint32_t s = r48::nt_stage(cuts, b);   // 0 .. cuts.n
+    if (s > seen[i]) {
+        const int64_t at = (int64_t)(s - 1u) * n + i;
+        store_board(pool, at, b);
+        pool_has[at] = 1;
+        seen[i] = (uint8_t)s;
+    }
+}
+
 // ---- the entry points ---------------------------------------------------------------------------
 
 // one pointer argument of an entry point: its name in the message, the alignment it needs, and
@@ -1442,6 +1508,34 @@ int nt_tc_rate(const char *fn, const int8_t *boards, int64_t n, const uint8_t *c
     });
 }
 
+int nt_carousel(const char *fn, int8_t *boards, int64_t n, const uint8_t *done, const uint8_t *cuts, int32_t n_cuts,
+                int8_t *pool, uint8_t *pool_has, uint8_t *seen, uint8_t *turn, uint64_t *starts, uint64_t seed, int64_t gid0,
+                uint32_t ctr, void *stream)
+{
+    for (const PtrArg &a : {PtrArg{"boards", boards, 16, true}, PtrArg{"done", done, 1, true}, PtrArg{"cuts", cuts, 1, true},
+                            PtrArg{"pool", pool, 16, true}, PtrArg{"pool_has", pool_has, 1, true},
+                            PtrArg{"seen", seen, 1, true}, PtrArg{"turn", turn, 1, true}, PtrArg{"starts", starts, 8, false}}) {
+        if (!a.p && a.required)
+            return fail(R48_EINVAL, std::string(fn) + ": " + a.name + " is NULL");
+        if (!aligned(a.p, a.align))
+            return fail(R48_EINVAL, std::string(fn) + ": " + a.name + " is not " + std::to_string(a.align) + "-byte aligned");
+    }
+    if (n < 0 || n > 0x7FFFFFFFll)
+        return fail(R48_EINVAL, std::string(fn) + ": n = " + std::to_string(n) + " boards, must be 0 .. 2^31 - 1 (the donor is a 32-bit draw)");
+    if (const char *why = r48::nt_carousel_cuts_check(cuts, n_cuts))
+        return fail(R48_EINVAL, std::string(fn) + ": bad cuts: " + why);
+    if (n == 0)
+        return R48_OK;
+    const r48::NtCuts c = r48::nt_cuts_pack(cuts, n_cuts);
+    launch(k_nt_carousel_restart, grid_for(n), kBlock, stream, boards, n, done, c, (const int8_t *)pool,
+           (const uint8_t *)pool_has, seen, turn, reinterpret_cast<unsigned long long *>(starts), (uint32_t)seed,
+           (uint32_t)(seed >> 32), gid0, ctr);
+    if (const int rc = launched("k_nt_carousel_restart"))
+        return rc;
+    launch(k_nt_carousel_record, grid_for(n), kBlock, stream, (const int8_t *)boards, n, done, c, pool, pool_has, seen);
+    return launched("k_nt_carousel_record");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1622,6 +1716,14 @@ int r48_ntuple_tc_rate_staged(const int8_t *boards, int64_t n, const uint8_t *ce
                               void *stream)
 {
     return nt_tc_rate("r48_ntuple_tc_rate_staged", boards, n, cells, m, L, cuts, n_cuts, tc_e, tc_a, rate_out, stream);
+}
+
+int r48_ntuple_carousel(int8_t *boards, int64_t n, const uint8_t *done, const uint8_t *cuts, int32_t n_cuts, int8_t *pool,
+                        uint8_t *pool_has, uint8_t *seen, uint8_t *turn, uint64_t *starts, uint64_t seed, int64_t gid0,
+                        uint32_t ctr, void *stream)
+{
+    return nt_carousel("r48_ntuple_carousel", boards, n, done, cuts, n_cuts, pool, pool_has, seen, turn, starts, seed, gid0,
+                       ctr, stream);
 }
 
 }  // extern "C"

@@ -25,6 +25,11 @@ evaluated. An entry of a higher stage that was never updated reads as the neares
 current value (the update copies new values upwards until the first entry that has its own), so a
 fresh stage does not read as 0, and its first update starts from there. Opt-in; stages=() is the
 single-stage net, unchanged.
+
+NTupleConfig.carousel=(c_1, ..., c_k) (cuts of the same form) turns on carousel shaping in the trainer
+(Jaskowski 2016): episodes start in turn from every stage, from a remembered board with which a
+recent episode entered it, so the late stages get as many episode starts as the first
+(NTupleTrainer; the contract is in rein48_amd/csrc/r48_ntuple.h). Opt-in; carousel=() is off.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -473,6 +478,7 @@ class NTupleConfig:
     tc: bool = False                 # temporal-coherence learning rates; alpha = 1.0 is recommended with it
     fused: bool = False              # train_step in three launches (td_act, apply, env.step): the same bits
     stages: tuple = ()               # cuts of a multi-stage net with weight promotion: () or 1..3 ascending exponents in 1..15
+    carousel: tuple = ()             # cuts of carousel shaping (episode starts in turn from every stage): () is off
 
 
 class NTupleTrainer:
@@ -487,6 +493,14 @@ class NTupleTrainer:
     step follow, and the "previous" buffers are swapped by reference: three launches and no torch
     kernel instead of about fourteen, the same bits in every tensor, so a checkpoint moves freely
     between the two paths.
+    cfg.carousel: carousel shaping (Jaskowski 2016). The cuts split a game into stages by the env
+    board's largest tile, as a staged net's cuts do (they need not be the net's, and the net may be
+    unstaged). Every board slot remembers the board with which its game last entered each stage, and
+    an episode that ends restarts in turn from stage 0 (the env's fresh board), 1, ..., S - 1, from
+    the remembered entry board of a slot drawn by Philox -- or from the fresh board where that slot
+    has none yet. One call (two launches) after the env step, in both paths; the TD chain is as it
+    was: the step after a restart takes target 0 for the ended episode's last afterstate. Off, the
+    trainer allocates and calls nothing more.
     No exploration: the spawns randomise. Single GPU (an all-reduce of the table updates is not
     built)."""
 
@@ -511,6 +525,35 @@ class NTupleTrainer:
         self.valid, self.prev_valid = (torch.zeros(n, dtype=torch.uint8, device=d) for _ in range(2))
         self.delta = torch.zeros(n, dtype=torch.float32, device=d)
         self.updates = 0
+        # carousel shaping: the entry boards per stage and slot, and where each slot's episode stands
+        self.carousel = stage_cuts(cfg.carousel)
+        if self.carousel:
+            S = len(self.carousel) + 1
+            self._carousel = (C.c_uint8 * len(self.carousel))(*self.carousel)
+            self.pool = torch.zeros((S - 1, n, 16), dtype=torch.int8, device=d)
+            self.pool_has = torch.zeros((S - 1, n), dtype=torch.uint8, device=d)
+            self.seen, self.turn = (torch.zeros(n, dtype=torch.uint8, device=d) for _ in range(2))
+            self.starts = torch.zeros(S, dtype=torch.int64, device=d)   # the library's uint64 words
+
+    # the carousel's tensors, as a checkpoint carries them
+    CAROUSEL_STATE = ("pool", "pool_has", "seen", "turn", "starts")
+
+    def _carousel_step(self, done):
+        """The carousel call after an env step with auto-reset: restarts where done, records elsewhere."""
+        env = self.env
+        check(self.net._lib.r48_ntuple_carousel(ptr(env.boards), env.n, ptr(done), self._carousel, len(self.carousel),
+                                                ptr(self.pool), ptr(self.pool_has), ptr(self.seen), ptr(self.turn),
+                                                ptr(self.starts), env.seed, env.board_offset,
+                                                self.updates & 0xFFFFFFFF, _stream(env.boards)))
+
+    def carousel_stats(self):
+        """{"starts": episode starts per stage since the trainer was built (or since the checkpoint's
+        trainer was), "filled": per stage the share of board slots whose pool slot holds an entry
+        board -- 1.0 for stage 0, which starts from the env's fresh board}."""
+        if not self.carousel:
+            raise ValueError("carousel_stats needs a trainer built with cfg.carousel")
+        return {"starts": [int(x) for x in self.starts.tolist()],
+                "filled": [1.0] + [float(x) for x in self.pool_has.float().mean(dim=1).tolist()]}
 
     @torch.no_grad()
     def train_step(self):
@@ -529,6 +572,8 @@ class NTupleTrainer:
             _, _, done = env.step(self.actions, auto_reset=True)
             self.prev_done.copy_(done)
             self.prev_valid.copy_(self.legal != 0)   # an afterstate exists where a move did
+        if self.carousel:
+            self._carousel_step(self.prev_done)
         # this step's afterstates and values become the previous ones
         self.after, self.prev_after = self.prev_after, self.after
         self.value, self.prev_value = self.prev_value, self.value

@@ -109,6 +109,15 @@ net on the same boards, --sizes boards (default 4096,65536), the two builds' win
 with the cuts (), (9,), (10,) and (8, 10): --episodes whole games at eval seed 13 at depths 1, 2 and 3, the share
 of games reaching 2,048 / 4,096 / 8,192 and the share of own[1] set. --no-kernels skips (a). Writes
 exp_ntuple_stages.json.
+
+With --carousel, carousel shaping (NTupleConfig.carousel): (a) the carousel call alone and the fused TC
+trainer's step with carousel=(10,) against the same trainer without, windows interleaved, after 300 steps of
+each, --sizes boards (default 1024,4096,65536); (b) with --scores, the 4x6 TC recipe of --stages for --budgets
+steps with stages (), (10,) and (8, 10), each without carousel and with the carousel on the net's cuts ((10,)
+for the unstaged net): --episodes whole games at eval seed 13 at depths 1, 2 and 3, the difference to the
+row without carousel in standard errors of the difference, own[k], carousel_stats() and the training's wall
+time; the rows without carousel are checked against the recorded exp_ntuple_stages.json
+(reproduces_recorded). --no-kernels skips (a). Writes exp_ntuple_carousel.json.
 """
 import argparse
 import json
@@ -1392,6 +1401,96 @@ def main_stages(args):
             json.dump(out, f, indent=1)
 
 
+def carousel_cost(layout, n, cuts=(10,), settle=300):
+    """The fused TC trainer's step (alpha 1.0) with carousel=cuts against the same trainer without, their
+    windows interleaved, after `settle` steps of each so that episodes end at the rate of a running
+    trainer; then the carousel call alone (both launches) on the carousel trainer's boards with its last
+    step's done flags."""
+    trs = {k: NTupleTrainer(NTupleConfig(n_boards=n, layout=layout, alpha=1.0, seed=3, tc=True, fused=True, carousel=c),
+                            device=DEV) for k, c in (("plain", ()), ("carousel", cuts))}
+    for tr in trs.values():
+        tr.train_steps(settle)
+    t = alternated_ms({k: tr.train_step for k, tr in trs.items()}, warmup=20)
+    tr = trs["carousel"]
+    res = {"layout": layout, "boards": n, "carousel": list(cuts), "settle_steps": settle,
+           "share_of_done": float((tr.prev_done != 0).float().mean()),
+           "train_step_fused": {"plain": _ms(t["plain"]), "carousel": _ms(t["carousel"]),
+                                "carousel_over_plain": t["carousel"][0] / t["plain"][0]},
+           "carousel_call": _ms(event_ms(lambda: tr._carousel_step(tr.prev_done)))}
+    del trs, tr
+    torch.cuda.empty_cache()
+    return res
+
+
+def carousel_scores(layout, n_boards, steps, stages, carousel, eval_seed=13, episodes=4096, depths=(1, 2, 3)):
+    """stage_scores with NTupleConfig.carousel: one budget of the fused TC trainer (alpha 1.0, seed 0), then
+    whole episodes at each depth; own[k] for every higher stage and carousel_stats()."""
+    tr = NTupleTrainer(NTupleConfig(n_boards=n_boards, layout=layout, alpha=1.0, seed=0, tc=True, fused=True, stages=stages,
+                                    carousel=carousel), device=DEV)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tr.train_steps(steps)
+    torch.cuda.synchronize()
+    row = {"layout": layout, "stages": list(stages), "carousel": list(carousel), "train_boards": n_boards,
+           "train_steps": steps, "eval_seed": eval_seed, "episodes": episodes, "train_seconds": time.perf_counter() - t0}
+    if stages:
+        row["share_of_own_set"] = [float(tr.net.own[k].float().mean()) for k in range(1, tr.net.S)]
+    if carousel:
+        row["carousel_stats"] = tr.carousel_stats()
+    for depth in depths:
+        t0 = time.perf_counter()
+        ev = tr.net.play_episodes(episodes, seed=eval_seed, depth=depth, return_scores=True)
+        sc = ev.pop("scores").numpy()
+        ev["score_std"] = float(sc.std(ddof=1))
+        ev["standard_error"] = ev["score_std"] / episodes ** 0.5
+        hist = ev["max_tile_exponent_hist"]
+        for e in (11, 12, 13):
+            ev["reach_%d" % (1 << e)] = sum(f for k, f in hist.items() if k >= e)
+        ev["eval_seconds"] = time.perf_counter() - t0
+        row["depth%d" % depth] = ev
+    del tr
+    torch.cuda.empty_cache()
+    return row
+
+
+def main_carousel(args):
+    """--carousel: what carousel shaping costs (--sizes boards, default 1024,4096,65536) and, with --scores,
+    what it scores: 4x6 TC at 4,096 boards for --budgets train steps (default 10000,40000), nets with stages (),
+    (10,) and (8, 10), each without carousel and with the carousel on the net's cuts ((10,) for the unstaged
+    net). The rows without carousel are compared with the recorded exp_ntuple_stages.json. Writes
+    exp_ntuple_carousel.json."""
+    out = {"device": torch.cuda.get_device_name(0), "cost": [], "scores": []}
+    if not args.no_kernels:
+        for layout in ("lines-squares", "4x6"):
+            for n in (int(s) for s in (args.sizes or "1024,4096,65536").split(",")):
+                r = carousel_cost(layout, n)
+                out["cost"].append(r)
+                print(json.dumps(r), flush=True)
+    if args.scores:
+        here = os.path.dirname(os.path.abspath(__file__))
+        with open(os.path.join(here, "..", "profiles", "ntuple", "exp_ntuple_stages.json")) as f:
+            recorded = {(tuple(r["cuts"]), r["train_steps"]): r for r in json.load(f)["scores"]}
+        for steps in (int(s) for s in args.budgets.split(",")):
+            for stages in ((), (10,), (8, 10)):
+                off = carousel_scores("4x6", 4096, steps, stages, (), episodes=args.episodes)
+                rec = recorded.get((stages, steps))
+                if rec is not None and args.episodes == rec["episodes"]:
+                    off["reproduces_recorded"] = all(off["depth%d" % d][k] == rec["depth%d" % d][k] for d in (1, 2, 3)
+                                                     for k in ("mean_score", "score_std", "mean_length"))
+                on = carousel_scores("4x6", 4096, steps, stages, stages or (10,), episodes=args.episodes)
+                for d in (1, 2, 3):
+                    a, b = on["depth%d" % d], off["depth%d" % d]
+                    se = (a["standard_error"] ** 2 + b["standard_error"] ** 2) ** 0.5
+                    a["vs_no_carousel_in_standard_errors"] = (a["mean_score"] - b["mean_score"]) / se
+                for r in (off, on):
+                    out["scores"].append(r)
+                    print(json.dumps(r), flush=True)
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        with open(os.path.join(args.out, "exp_ntuple_carousel.json"), "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main_search(args):
     out = {"device": torch.cuda.get_device_name(0), "kernels": [], "scores": []}
     for layout in ("lines-squares", "4x6"):
@@ -1432,9 +1531,12 @@ def main():
     ap.add_argument("--stages", action="store_true")
     ap.add_argument("--budgets", default="10000,40000")
     ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--carousel", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("exp_ntuple.py needs a GPU")
+    if args.carousel:
+        return main_carousel(args)
     if args.stages:
         return main_stages(args)
     if args.play_ruled:
