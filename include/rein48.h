@@ -527,7 +527,8 @@ int r48_struct_conv_weight_grad(const void *gdense, int32_t co, int32_t ci, int3
  * aligned, C in {32, 64, 128}; gamma, beta, running statistics, dgamma, dbeta: float[C].
  * Forward: y = relu?(gamma (x - mean) invstd + beta (+ residual)) with the batch statistics over
  * rows (biased variance), running_mean/var (nullable together) updated with `momentum` and the
- * unbiased variance, save = float[2 C] {mean, invstd} for the backward. Backward: given dy
+ * unbiased variance n / (n - 1) var (rows = 1: var itself, which is 0; torch refuses a single row),
+ * save = float[2 C] {mean, invstd} for the backward. Backward: given dy
  * (gradient of y) and the saved y (ReLU mask, when relu) -> dx, dgamma, dbeta (nullable) and
  * dresidual (nullable: the gradient reaching the residual input). workspace: float[
  * r48_bn_workspace_floats(rows, C)], not shared between calls in flight. Deterministic.

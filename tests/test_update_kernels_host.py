@@ -3,13 +3,15 @@ the CPU: a wrong reference must not be able to agree with a wrong kernel in test
 
 Huber against torch's smooth_l1_loss and autograd, Adam against torch.optim.Adam, the returns slab
 against the reference's own executed outputs (tests/golden/a3c_golden.json), the vectorised Philox
-against the C oracle's. RMSProp and the TD target are oracle/a3c_ref.py's and oracle/dqn_ref.py's,
+against the C oracle's, the BatchNorm forward and backward (test_bn_kernels_gpu.py's references) against
+torch's batch_norm and autograd. RMSProp and the TD target are oracle/a3c_ref.py's and oracle/dqn_ref.py's,
 which test_a3c.py and test_dqn.py cover.
 """
 import json
 import os
 
 import numpy as np
+import pytest
 import torch
 
 import update_refs as U
@@ -117,6 +119,79 @@ def test_sample_uniforms_follow_the_draw_contract():
         g = gid0 + i
         w = O.philox([g & 0xFFFFFFFF, g >> 32, ctr, 0xA3C], [seed & 0xFFFFFFFF, seed >> 32])
         assert u[i] == (int(w[0]) >> 8) / 16777216.0 and 0.0 <= u[i] < 1.0
+
+
+def _bn_host_case(n, C, seed):
+    """bf16-valued x, res, g [n, C] and gamma, beta, rm, rv [C] in float64. Channel 1 is constant,
+    channel 2 has |mean| / std = 128, gamma is 0 in channel 3 and negative in channel 4."""
+    gen = torch.Generator().manual_seed(seed)
+    mu, sd = torch.randn(C, generator=gen) * 2, torch.rand(C, generator=gen) + 0.5
+    mu[2], sd[2] = 0.998, 0.998 / 128
+    x = torch.randn(n, C, generator=gen) * sd + mu
+    x[:, 1] = 1.5
+    x, res, g = (t.to(torch.bfloat16).double() for t in (x, torch.randn(n, C, generator=gen), torch.randn(n, C, generator=gen)))
+    gamma, beta = torch.randn(C, generator=gen).double() + 1, torch.randn(C, generator=gen).double()
+    gamma[3], gamma[4] = 0.0, -1.25
+    return x, res, g, gamma, beta, torch.randn(C, generator=gen).double(), torch.rand(C, generator=gen).double() + 0.5
+
+
+@pytest.mark.parametrize("n", [2, 3, 257])
+@pytest.mark.parametrize("with_res,relu", [(False, False), (False, True), (True, False), (True, True)])
+@pytest.mark.parametrize("momentum,eps", [(0.1, 1e-5), (1.0, 1e-3)])
+def test_bn_references_match_torch_batch_norm_and_autograd(n, with_res, relu, momentum, eps):
+    """update_refs.bn_forward / bn_backward against torch.nn.functional.batch_norm (training mode)
+    + add + ReLU and autograd, float64 on the CPU: rtol 1e-12, with an absolute 1e-13 of the largest
+    entry for the entries that cancel to nearly nothing (a constant channel's dgamma is 0 up to the
+    last bit of its mean). bn_backward gets the gradient through the ReLU of the reference's own y."""
+    C = 8
+    x, res, dy, gamma, beta, rm, rv = _bn_host_case(n, C, 10 * n + relu)
+    f = U.bn_forward(x.numpy(), res.numpy() if with_res else None, gamma.numpy(), beta.numpy(), rm.numpy(), rv.numpy(),
+                     momentum, eps, relu)
+    tx, tg, tb = (t.clone().requires_grad_(True) for t in (x, gamma, beta))
+    tr = res.clone().requires_grad_(True)
+    trm, trv = rm.clone(), rv.clone()
+    z = torch.nn.functional.batch_norm(tx, trm, trv, tg, tb, True, momentum, eps)
+    if with_res:
+        z = z + tr
+    y = torch.relu(z) if relu else z
+    y.backward(dy)
+
+    def close(got, want):
+        want = want.detach().numpy() if torch.is_tensor(want) else want
+        np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-13 * np.abs(want).max())
+    close(f["y"], y)
+    close(f["rm"], trm)
+    close(f["rv"], trv)
+    close(f["mean"], x.mean(0))
+    close(f["var"], x.var(0, unbiased=False))
+    close(f["z"], f["a"] * x.numpy() + f["b"] + (res.numpy() if with_res else 0.0))
+    assert f["var"][1] == 0 and f["mean"][1] == 1.5 and f["invstd"][1] == 1.0 / np.sqrt(eps)
+    assert 100 < abs(f["mean"][2]) / np.sqrt(f["var"][2]) < 200 or n < 257
+    g = dy.numpy() * (f["y"] > 0) if relu else dy.numpy()
+    b = U.bn_backward(g, x.numpy(), f["mean"], f["invstd"], gamma.numpy())
+    close(b["dx"], tx.grad)
+    close(b["dgamma"], tg.grad)
+    close(b["dbeta"], tb.grad)
+    if with_res:
+        close(g, tr.grad)
+    mag = np.abs(b["a"] * g) + np.abs(b["cc"] * x.numpy()) + np.abs(b["d"])
+    assert (np.abs(b["a"] * g + b["cc"] * x.numpy() + b["d"] - b["dx"]) <= 1e-14 * mag).all()
+    assert b["dgamma"][1] == 0 and (b["dx"][:, 3] == 0).all()
+    np.testing.assert_array_equal(b["g_mag"], np.abs(g).sum(0))
+    np.testing.assert_array_equal(b["gx_mag"], (np.abs(g) * np.abs(x.numpy() - f["mean"])).sum(0))
+    s = U.bn_from_sums(x.numpy().sum(0), np.square(x.numpy()).sum(0), n, 0.0, gamma.numpy(), beta.numpy(), rm.numpy(),
+                       rv.numpy(), momentum, eps)
+    for k in ("mean", "a", "rm"):                # plain sums lose 128^2 of the variance's digits in channel 2
+        np.testing.assert_allclose(s[k], f[k], rtol=1e-12 * (16384 if k == "a" else 1), atol=1e-13)
+    np.testing.assert_allclose(s["var"], f["var"], rtol=0, atol=1e-13 * np.square(x.numpy()).mean(0).max())
+
+
+def test_bn_reference_single_row_takes_the_variance_itself():
+    """n = 1: var = 0, and the running variance moves towards var itself (no n / (n - 1))."""
+    x = np.array([[1.5, -2.0]])
+    f = U.bn_forward(x, None, np.ones(2), np.zeros(2), np.zeros(2), np.ones(2), 0.25, 1e-5, False)
+    assert (f["var"] == 0).all() and (f["mean"] == x[0]).all() and (f["rv"] == 0.75).all() and (f["y"] == 0).all()
+    assert U.bn_forward(x, None, np.ones(2), np.zeros(2), None, None, 0.25, 1e-5, False)["rm"] is None
 
 
 def test_bf16_half_ulp_bounds_round_to_nearest():

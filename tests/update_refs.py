@@ -8,6 +8,9 @@ test_update_kernels_host.py (which checks these references on the CPU) and test_
   adam            one torch.optim.Adam step (bias-corrected, eps outside the square root)
   returns         r48_discounted_returns' [T][n] slab, lengths clamped to 0..T
   q_head          the Q head Linear(1024 -> 4) and its backward, with the magnitude sums of the bounds
+  bn_forward      training-mode BatchNorm (+ residual, ReLU): statistics, coefficients, output, running
+                  statistics (bn_from_sums: the same from given sums), with the bounds' magnitude sums
+  bn_backward     its backward from the masked gradient (bn_backward_from_sums: from given sums)
 RMSProp and the TD target are oracle/a3c_ref.py's and oracle/dqn_ref.py's.
 """
 import numpy as np
@@ -86,3 +89,68 @@ def bf16_half_ulp(x):
     x = np.abs(np.asarray(x, np.float64))
     _, e = np.frexp(x)                                        # x = f 2^e, f in [0.5, 1)
     return np.where(x > 0, np.ldexp(1.0, e - 1 - 8), 0.0)
+
+
+def _bn_coefs(mean, var, n, gamma, beta, rm, rv, momentum, eps):
+    """The finish of a training-mode BatchNorm from a channel's mean and biased variance over n rows:
+    invstd, a = gamma invstd, b = beta - mean a, and the running statistics (None without rm). The
+    running variance takes the unbiased n / (n - 1) var for n > 1 and var itself for n = 1 (the
+    kernels' choice: torch refuses n = 1)."""
+    invstd = 1.0 / np.sqrt(var + eps)
+    a = gamma * invstd
+    out = {"mean": mean, "var": var, "invstd": invstd, "a": a, "b": beta - mean * a, "rm": None, "rv": None}
+    if rm is not None:
+        unb = var * (n / (n - 1.0)) if n > 1 else var
+        out["rm"] = (1.0 - momentum) * rm + momentum * mean
+        out["rv"] = (1.0 - momentum) * rv + momentum * unb
+    return out
+
+
+def bn_from_sums(s1, s2, n, x0, gamma, beta, rm, rv, momentum, eps):
+    """From s1 = sum (x - x0) and s2 = sum (x - x0)^2 per channel over n rows (x0 = 0: plain sums):
+    mean = x0 + s1 / n, var = max(s2 / n - (s1 / n)^2, 0) and _bn_coefs of them, float64."""
+    dm = s1 / n
+    return _bn_coefs(x0 + dm, np.maximum(s2 / n - dm * dm, 0.0), n, gamma, beta, rm, rv, momentum, eps)
+
+
+def bn_forward(x, res, gamma, beta, rm, rv, momentum, eps, relu):
+    """x [n, C], res [n, C] or None, gamma, beta, rm, rv [C] (rm, rv None together), float64 holding
+    the values the kernels see. -> dict: mean, var (biased, two passes), invstd, a, b, z = a x + b
+    (+ res), y = relu?(z), rm, rv after the momentum update, and the magnitudes of the bounds:
+    s1_mag = sum |x - x0|, s2_mag = sum (x - x0)^2 (x0 = row 0, the kernels' shift) and
+    z_mag = |a x| + |b| + |res|."""
+    n = x.shape[0]
+    mean = x.mean(0)
+    out = _bn_coefs(mean, np.square(x - mean).mean(0), n, gamma, beta, rm, rv, momentum, eps)
+    z = out["a"] * x + out["b"]
+    mag = np.abs(out["a"] * x) + np.abs(out["b"])
+    if res is not None:
+        z = z + res
+        mag += np.abs(res)
+    d0 = x - x[0]
+    out.update(z=z, y=np.maximum(z, 0.0) if relu else z, z_mag=mag, s1_mag=np.abs(d0).sum(0),
+               s2_mag=np.square(d0).sum(0))
+    return out
+
+
+def bn_backward_from_sums(sg, sgx, n, mean, invstd, gamma):
+    """From sg = sum g and sgx = sum g (x - mean) per channel: dbeta = sg, dgamma = invstd sgx and the
+    coefficients of dx = a g + cc x + d: a = gamma invstd, cc = -a invstd dgamma / n,
+    d = -a dbeta / n - cc mean."""
+    dgamma = invstd * sgx
+    a = gamma * invstd
+    cc = -a * invstd * dgamma / n
+    return {"dbeta": sg, "dgamma": dgamma, "a": a, "cc": cc, "d": -a * sg / n - cc * mean}
+
+
+def bn_backward(g, x, mean, invstd, gamma):
+    """g [n, C] (the output gradient already through the ReLU mask), x [n, C], mean, invstd, gamma [C],
+    float64. -> dict: dbeta, dgamma, a, cc, d (bn_backward_from_sums), dx = a g + cc x + d -- evaluated
+    as a (g - dbeta / n - (x - mean) invstd dgamma / n), the same number without the cancellation of
+    cc x + d when |mean| >> std -- and the magnitudes g_mag = sum |g|, gx_mag = sum |g| |x - mean|."""
+    n = x.shape[0]
+    xc = x - mean
+    out = bn_backward_from_sums(g.sum(0), (g * xc).sum(0), n, mean, invstd, gamma)
+    out.update(dx=out["a"] * (g - out["dbeta"] / n - xc * (invstd * out["dgamma"] / n)),
+               g_mag=np.abs(g).sum(0), gx_mag=(np.abs(g) * np.abs(xc)).sum(0))
+    return out
