@@ -18,17 +18,18 @@
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
+#include "r48_host.h"
 #include "r48_select.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::aligned16;
+using r48::all_aligned16;
+using r48::fail;
+using r48::grid_for;
+using r48::launched;
 
 namespace {
 
 constexpr int kBlock = 256;
-
-inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
 template <int MODE>
 __device__ __forceinline__ float cell_feature(uint32_t e)
@@ -192,22 +193,6 @@ __global__ __launch_bounds__(kBlock) void k_rmsprop_tf1(float *__restrict__ var,
     var[i] -= u;
 }
 
-int fail(int code, const char *msg)
-{
-    r48::set_last_error(msg);  // the thread-local message behind r48_last_error (r48_env.hip)
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        r48::set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-        return R48_EHIP;
-    }
-    return R48_OK;
-}
-
 // Per-segment constants of the A3C loss (losses.segment_stats, a3c.py:99-123) for segments of
 // length len[i] (mask = t < len[i]): B[i] = max(len[i], 1); td_sum[i] = sum over t < len[i] of
 // targets[t][i] - values[t][i]; counts[i][k] = #{t < len[i] : actions[t][i] == k}. One lane per
@@ -352,21 +337,21 @@ int r48_board_features(const int8_t *boards, int64_t n, int32_t mode, int32_t ou
     if (!boards || !out || n < 0 || (mode != R48_FEAT_VALUES && mode != R48_FEAT_EXPONENTS) ||
         (out_dtype != R48_F32 && out_dtype != R48_BF16))
         return fail(R48_EINVAL, "boards/out NULL, n < 0, or bad mode/dtype");
-    if ((reinterpret_cast<uintptr_t>(boards) | reinterpret_cast<uintptr_t>(out)) & 15u)
+    if (!all_aligned16(boards, out))
         return fail(R48_EINVAL, "boards and out must be 16-byte aligned");
     if (n == 0)
         return R48_OK;
     const hipStream_t s = (hipStream_t)stream;
     if (out_dtype == R48_F32) {
         if (mode == R48_FEAT_VALUES)
-            hipLaunchKernelGGL(k_features_f32<0>, grid_for(n), dim3(kBlock), 0, s, boards, n, (float *)out);
+            hipLaunchKernelGGL(k_features_f32<0>, grid_for(n, kBlock), dim3(kBlock), 0, s, boards, n, (float *)out);
         else
-            hipLaunchKernelGGL(k_features_f32<1>, grid_for(n), dim3(kBlock), 0, s, boards, n, (float *)out);
+            hipLaunchKernelGGL(k_features_f32<1>, grid_for(n, kBlock), dim3(kBlock), 0, s, boards, n, (float *)out);
     } else {
         if (mode == R48_FEAT_VALUES)
-            hipLaunchKernelGGL(k_features_bf16<0>, grid_for(n), dim3(kBlock), 0, s, boards, n, (uint16_t *)out);
+            hipLaunchKernelGGL(k_features_bf16<0>, grid_for(n, kBlock), dim3(kBlock), 0, s, boards, n, (uint16_t *)out);
         else
-            hipLaunchKernelGGL(k_features_bf16<1>, grid_for(n), dim3(kBlock), 0, s, boards, n, (uint16_t *)out);
+            hipLaunchKernelGGL(k_features_bf16<1>, grid_for(n, kBlock), dim3(kBlock), 0, s, boards, n, (uint16_t *)out);
     }
     return launched("k_features");
 }
@@ -376,11 +361,11 @@ int r48_sample_actions(const float *logits, int64_t n, uint64_t seed, int64_t gi
 {
     if (!logits || !actions || n < 0 || gid0 < 0)
         return fail(R48_EINVAL, "logits/actions NULL or n/gid0 < 0");
-    if (reinterpret_cast<uintptr_t>(logits) & 15u)
+    if (!aligned16(logits))
         return fail(R48_EINVAL, "logits must be 16-byte aligned");
     if (n == 0)
         return R48_OK;
-    hipLaunchKernelGGL(k_sample, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, logits, n, gid0, (uint32_t)seed,
+    hipLaunchKernelGGL(k_sample, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, logits, n, gid0, (uint32_t)seed,
                        (uint32_t)(seed >> 32), ctr, actions, logp, entropy);
     return launched("k_sample");
 }
@@ -392,7 +377,7 @@ int r48_rmsprop_tf1(float *var, const float *grad, float *ms, float *mom, int64_
         return fail(R48_EINVAL, "NULL argument or n < 0");
     if (n == 0)
         return R48_OK;
-    hipLaunchKernelGGL(k_rmsprop_tf1, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, var, grad, ms, mom, n, lr,
+    hipLaunchKernelGGL(k_rmsprop_tf1, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, var, grad, ms, mom, n, lr,
                        decay, momentum, eps);
     return launched("k_rmsprop_tf1");
 }
@@ -404,16 +389,15 @@ int r48_discounted_returns(const float *rewards, const int32_t *lengths, const f
         return fail(R48_EINVAL, "NULL argument, T < 1 or n < 0");
     if (n == 0)
         return R48_OK;
-    if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(rewards) | reinterpret_cast<uintptr_t>(lengths) |
-                          reinterpret_cast<uintptr_t>(bootstrap) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0) {
+    if ((n & 3) == 0 && all_aligned16(rewards, lengths, bootstrap, out)) {
         auto k4 = drop_last ? k_returns4<true> : k_returns4<false>;
-        hipLaunchKernelGGL(k4, grid_for(n / 4), dim3(kBlock), 0, (hipStream_t)stream, (const float4 *)rewards,
+        hipLaunchKernelGGL(k4, grid_for(n / 4, kBlock), dim3(kBlock), 0, (hipStream_t)stream, (const float4 *)rewards,
                            (const int4 *)lengths, (const float4 *)bootstrap, T, n / 4, gamma, (float4 *)out);
     } else if (drop_last)
-        hipLaunchKernelGGL(k_returns<true>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, rewards, lengths,
+        hipLaunchKernelGGL(k_returns<true>, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, rewards, lengths,
                            bootstrap, T, n, gamma, out);
     else
-        hipLaunchKernelGGL(k_returns<false>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, rewards, lengths,
+        hipLaunchKernelGGL(k_returns<false>, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, rewards, lengths,
                            bootstrap, T, n, gamma, out);
     return launched("k_returns");
 }
@@ -423,16 +407,16 @@ int r48_a3c_segment_stats(const float *values, const float *targets, const int8_
 {
     const bool td = td_sum != nullptr;
     if (!actions || !lengths || !B || !counts || T < 1 || n < 0 || (td && (!values || !targets)) ||
-        (reinterpret_cast<uintptr_t>(counts) & 15))
+        !aligned16(counts))
         return fail(R48_EINVAL, "r48_a3c_segment_stats: NULL argument (values/targets needed with td_sum), T < 1, "
                                 "n < 0 or counts not 16-byte aligned");
     if (n == 0)
         return R48_OK;
     if (td)
-        hipLaunchKernelGGL(k_segment_stats<true>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, values, targets,
+        hipLaunchKernelGGL(k_segment_stats<true>, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, values, targets,
                            actions, lengths, T, n, B, td_sum, reinterpret_cast<float4 *>(counts));
     else
-        hipLaunchKernelGGL(k_segment_stats<false>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, values, targets,
+        hipLaunchKernelGGL(k_segment_stats<false>, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, values, targets,
                            actions, lengths, T, n, B, td_sum, reinterpret_cast<float4 *>(counts));
     return launched("k_segment_stats");
 }
@@ -458,14 +442,14 @@ int r48_a3c_segments(const float *rewards, const float *values, const int8_t *ac
 {
     const bool td = counts != nullptr;
     if (!rewards || !lengths || !bootstrap || !targets || !seg || T < 1 || n < 0 || (td && (!values || !actions)) ||
-        ((reinterpret_cast<uintptr_t>(seg) | reinterpret_cast<uintptr_t>(counts)) & 15))
+        !all_aligned16(seg, counts))
         return fail(R48_EINVAL, "r48_a3c_segments: NULL argument (values/actions needed with counts), T < 1, n < 0 "
                                 "or seg/counts not 16-byte aligned");
     if (n == 0)
         return R48_OK;
     auto kern = drop_last ? (td ? k_segments<true, true> : k_segments<true, false>)
                           : (td ? k_segments<false, true> : k_segments<false, false>);
-    hipLaunchKernelGGL(kern, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, rewards, values, actions, lengths,
+    hipLaunchKernelGGL(kern, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, rewards, values, actions, lengths,
                        bootstrap, T, n, gamma, targets, reinterpret_cast<float4 *>(seg), reinterpret_cast<float4 *>(counts));
     return launched("k_segments");
 }

@@ -55,9 +55,9 @@
 #include "r48_cnn_common.h"
 #include "r48_host.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::all_aligned16;
+using r48::fail;
+using r48::launched;
 
 namespace {
 
@@ -779,12 +779,6 @@ __global__ __launch_bounds__(256) void k_reduce(const float *__restrict__ group_
     out[k] = s;
 }
 
-int fail(int code, const std::string &msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
 // the persistent grid: one workgroup per CU of the stream's device, at most kMaxGrid (the MI355X's
 // 256 CUs) -- the per-wave record workspace (r48_cnn_train_workspace_floats) is sized for kMaxGrid,
 // so it covers any device (a compute partition with fewer CUs launches fewer workgroups, each
@@ -811,10 +805,7 @@ int cnn_train_launch(const int8_t *boards, int64_t rows, int64_t n_boards, const
     hipLaunchKernelGGL(k_reduce_groups, dim3((kPartial + 255) / 256, kGroups), dim3(256), 0, (hipStream_t)stream,
                        workspace, (int64_t)grid * kWaves, group_sums);
     hipLaunchKernelGGL(k_reduce, dim3((kPartial + 255) / 256), dim3(256), 0, (hipStream_t)stream, group_sums, grad);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(R48_EHIP, std::string("k_cnn_train: ") + hipGetErrorString(e));
-    return R48_OK;
+    return launched("k_cnn_train");
 }
 }  // namespace
 
@@ -833,8 +824,7 @@ int r48_cnn_train_grad(const int8_t *boards, int64_t rows, int64_t n_boards, con
     if (!boards || !actions || !targets || !wn || !wfrag || !bias || !workspace || !grad || rows < 1 ||
         n_boards < 1 || (mode != R48_FEAT_VALUES && mode != R48_FEAT_EXPONENTS) || (cm && !counts))
         return fail(R48_EINVAL, "NULL argument, rows/n_boards < 1, bad mode, or cm without counts");
-    if ((reinterpret_cast<uintptr_t>(boards) | reinterpret_cast<uintptr_t>(wfrag) |
-         reinterpret_cast<uintptr_t>(counts)) & 15u)
+    if (!all_aligned16(boards, wfrag, counts))
         return fail(R48_EINVAL, "boards, wfrag and counts must be 16-byte aligned");
     return cnn_train_launch(boards, rows, n_boards, actions, targets, wn, cm, nullptr, counts, beta, mode, wfrag, bias,
                             workspace, grad, stream);
@@ -847,8 +837,7 @@ int r48_cnn_train_grad_seg(const int8_t *boards, int64_t rows, int64_t n_boards,
     if (!boards || !actions || !targets || !seg || !wfrag || !bias || !workspace || !grad || rows < 1 ||
         n_boards < 1 || n_boards > 0x7FFFFFFF || (mode != R48_FEAT_VALUES && mode != R48_FEAT_EXPONENTS))
         return fail(R48_EINVAL, "NULL argument, rows/n_boards < 1, n_boards >= 2^31 or bad mode");
-    if ((reinterpret_cast<uintptr_t>(boards) | reinterpret_cast<uintptr_t>(wfrag) | reinterpret_cast<uintptr_t>(seg) |
-         reinterpret_cast<uintptr_t>(counts)) & 15u)
+    if (!all_aligned16(boards, wfrag, seg, counts))
         return fail(R48_EINVAL, "boards, wfrag, seg and counts must be 16-byte aligned");
     return cnn_train_launch(boards, rows, n_boards, actions, targets, nullptr, nullptr, seg, counts, beta, mode, wfrag,
                             bias, workspace, grad, stream);

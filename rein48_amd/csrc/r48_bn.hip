@@ -25,10 +25,11 @@
 
 #include "../../include/rein48.h"
 #include "r48_bn_finish.h"
+#include "r48_host.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::aligned16;
+using r48::fail;
+using r48::launched;
 
 namespace {
 
@@ -38,22 +39,6 @@ constexpr int kUnroll = 4;         // independent 16-B loads in flight per threa
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-int fail(int code, const char *msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        r48::set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-        return R48_EHIP;
-    }
-    return R48_OK;
-}
 
 __device__ __forceinline__ void unpack8(const uint4 v, float f[8])
 {
@@ -414,8 +399,6 @@ int apply_blocks(int64_t rows, int C)
     int64_t b = (rows + rpb - 1) / rpb;
     return (int)(b < 1 ? 1 : (b > 0x7FFFFFFF ? 0x7FFFFFFF : b));
 }
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 int check_args(const void *x, int64_t rows, int32_t C)
 {

@@ -30,10 +30,12 @@
 
 #include "../../include/rein48.h"
 #include "r48_bn_finish.h"
+#include "r48_host.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::aligned16;
+using r48::all_aligned16;
+using r48::fail;
+using r48::launched;
 
 namespace {
 
@@ -61,22 +63,6 @@ __device__ __forceinline__ bf16x8 as_frag(const uint4 &v) { return __builtin_bit
 __device__ __forceinline__ uint32_t pack2(float lo, float hi)
 {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2{lo, hi}), bf16x2_t));
-}
-
-int fail(int code, const std::string &msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        r48::set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-        return R48_EHIP;
-    }
-    return R48_OK;
 }
 
 // Persistent grids and their per-workgroup record buffers use ONE fixed workgroup count -- the
@@ -936,7 +922,7 @@ extern "C" {
 
 int r48_board_onehot32(const int8_t *boards, int64_t n, void *out, void *stream)
 {
-    if (!boards || !out || n < 0 || (reinterpret_cast<uintptr_t>(out) & 15u))
+    if (!boards || !out || n < 0 || !aligned16(out))
         return fail(R48_EINVAL, "r48_board_onehot32: NULL argument, n < 0 or out not 16-byte aligned");
     if (n == 0)
         return R48_OK;
@@ -955,8 +941,7 @@ int r48_conv3x3_stats_finish(const void *x, int64_t boards, int32_t cin, const v
     if (!x || !wfrag || !y || !stats || !fin || !fin->gamma || !fin->beta || !fin->save || !fin->coef || boards < 1 ||
         (cin != 32 && cin != 64) || fin->rows < 1)
         return fail(R48_EINVAL, "r48_conv3x3_stats_finish: NULL argument, boards < 1, rows < 1 or cin not 32/64");
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wfrag) | reinterpret_cast<uintptr_t>(y) |
-         reinterpret_cast<uintptr_t>(bias)) & 15u)
+    if (!all_aligned16(x, wfrag, y, bias))
         return fail(R48_EINVAL, "r48_conv3x3_stats_finish: x, wfrag, bias and y must be 16-byte aligned");
     if ((fin->running_mean == nullptr) != (fin->running_var == nullptr))
         return fail(R48_EINVAL, "r48_conv3x3_stats_finish: running_mean and running_var go together");
@@ -978,8 +963,7 @@ int r48_conv3x3(const void *x, int64_t boards, int32_t cin, const void *wfrag, c
 {
     if (!x || !wfrag || !y || boards < 1 || (cin != 32 && cin != 64))
         return fail(R48_EINVAL, "r48_conv3x3: NULL argument, boards < 1 or cin not 32/64");
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wfrag) | reinterpret_cast<uintptr_t>(y) |
-         reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(add)) & 15u)
+    if (!all_aligned16(x, wfrag, y, bias, add))
         return fail(R48_EINVAL, "r48_conv3x3: x, wfrag, bias, add and y must be 16-byte aligned");
     if (add && (cin != 64 || stats))
         return fail(R48_EINVAL, "r48_conv3x3: add needs 64 input channels and no stats");
@@ -1017,9 +1001,7 @@ int r48_conv3x3_bn_in(const void *x, int64_t boards, const void *wfrag, const fl
     const r48_bn_finish_args f = fin ? *fin : r48_bn_finish_args{};
     if (!x || !wfrag || !coef || !z_out || !mask_out || !y || !stats || boards < 1)
         return fail(R48_EINVAL, "r48_conv3x3_bn_in: NULL argument or boards < 1");
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wfrag) | reinterpret_cast<uintptr_t>(y) |
-         reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(coef) | reinterpret_cast<uintptr_t>(residual) |
-         reinterpret_cast<uintptr_t>(z_out)) & 15u)
+    if (!all_aligned16(x, wfrag, y, bias, coef, residual, z_out))
         return fail(R48_EINVAL, "r48_conv3x3_bn_in: x, wfrag, bias, coef, residual, z_out and y must be 16-byte aligned");
     const dim3 g(cu_count()), blk(64 * kConvWaves);
     hipStream_t s = (hipStream_t)stream;
@@ -1045,9 +1027,7 @@ int r48_conv3x3_bn_grad(const void *dy, int64_t boards, const void *wfrag, const
         return fail(R48_EINVAL, "r48_conv3x3_bn_grad: add_mask without add");
     if (!dy || !wfrag || !dx || !bn_x || !bn_mask || !bn_save || !bn_part || boards < 1)
         return fail(R48_EINVAL, "r48_conv3x3_bn_grad: NULL argument or boards < 1");
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(wfrag) | reinterpret_cast<uintptr_t>(dx) |
-         reinterpret_cast<uintptr_t>(add) | reinterpret_cast<uintptr_t>(bn_x) | reinterpret_cast<uintptr_t>(bn_save)) &
-        15u)
+    if (!all_aligned16(dy, wfrag, dx, add, bn_x, bn_save))
         return fail(R48_EINVAL, "r48_conv3x3_bn_grad: dy, wfrag, add, dx, bn_x and bn_save must be 16-byte aligned");
     const dim3 g(cu_count()), blk(64 * kConvWaves);
     hipStream_t s = (hipStream_t)stream;
@@ -1076,8 +1056,7 @@ int r48_conv3x3_wgrad(const void *dy, const void *x, int64_t boards, int32_t cin
 {
     if (!dy || !x || !workspace || !dw || boards < 1 || (cin != 32 && cin != 64))
         return fail(R48_EINVAL, "r48_conv3x3_wgrad: NULL argument, boards < 1 or cin not 32/64");
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace)) &
-        15u)
+    if (!all_aligned16(dy, x, workspace))
         return fail(R48_EINVAL, "r48_conv3x3_wgrad: dy, x and workspace must be 16-byte aligned");
     const int grid = cu_count();
     static_assert(kPersistentGroups <= kRedGroup * kRedGroup, "records_sum16 sums at most 256 records");
@@ -1107,7 +1086,7 @@ int r48_q_head_forward(const void *h, int64_t boards, const void *w, const float
 {
     if (!h || !w || !bias || !q || boards < 1)
         return fail(R48_EINVAL, "r48_q_head_forward: NULL argument or boards < 1");
-    if ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(q)) & 15u)
+    if (!all_aligned16(h, w, q))
         return fail(R48_EINVAL, "r48_q_head_forward: h, w and q must be 16-byte aligned");
     const int64_t want = (boards + kHeadWaves * kHeadUnroll - 1) / (kHeadWaves * kHeadUnroll);
     const int grid = (int)(want < 2 * cu_count() ? want : 2 * cu_count());
@@ -1121,9 +1100,7 @@ int r48_q_head_backward(const float *dq, const void *h, int64_t boards, const vo
 {
     if (!dq || !h || !w || !dh || !workspace || !dw || boards < 1)
         return fail(R48_EINVAL, "r48_q_head_backward: NULL argument or boards < 1");
-    if ((reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(w) |
-         reinterpret_cast<uintptr_t>(dh) | reinterpret_cast<uintptr_t>(workspace) |
-         reinterpret_cast<uintptr_t>(dw)) & 15u)
+    if (!all_aligned16(dq, h, w, dh, workspace, dw))
         return fail(R48_EINVAL, "r48_q_head_backward: all pointers must be 16-byte aligned");
     const int grid = cu_count();
     const int len4 = kHeadRec / 4;
@@ -1137,7 +1114,7 @@ int r48_q_head_backward(const float *dq, const void *h, int64_t boards, const vo
 
 int r48_conv_pack_resnet(const float *const *weights, void *fwd, void *dgrad, void *stream)
 {
-    if (!weights || !fwd || !dgrad || ((reinterpret_cast<uintptr_t>(fwd) | reinterpret_cast<uintptr_t>(dgrad)) & 15u))
+    if (!weights || !fwd || !dgrad || !all_aligned16(fwd, dgrad))
         return fail(R48_EINVAL, "r48_conv_pack_resnet: NULL or misaligned argument");
     hipLaunchKernelGGL(k_conv_pack, dim3(9 * 4 * 2 * 512 / 256, kPackParts), dim3(256), 0, (hipStream_t)stream, weights,
                        (uint16_t *)fwd, (uint16_t *)dgrad);

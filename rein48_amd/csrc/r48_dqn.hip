@@ -19,34 +19,18 @@
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
+#include "r48_host.h"
 #include "r48_select.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::aligned16;
+using r48::fail;
+using r48::grid_for;
+using r48::launched;
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kPlanes = 18;
-
-inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
-int fail(int code, const char *msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        r48::set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-        return R48_EHIP;
-    }
-    return R48_OK;
-}
 
 // one lane per (board, position): writes 18 values (36 B bf16 / 72 B f32)
 template <typename T>
@@ -233,8 +217,6 @@ __global__ __launch_bounds__(kBlock) void k_struct_weight_grad(const T *__restri
     gw[((int64_t)o * ci + i) * 9 + tap] = s;
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -247,10 +229,10 @@ int r48_board_onehot(const int8_t *boards, int64_t n, int32_t out_dtype, void *o
         return R48_OK;
     const int64_t cells = 16 * n;
     if (out_dtype == R48_F32)
-        hipLaunchKernelGGL(k_onehot<float>, grid_for(cells), dim3(kBlock), 0, (hipStream_t)stream, boards, cells,
+        hipLaunchKernelGGL(k_onehot<float>, grid_for(cells, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, cells,
                            (float *)out);
     else
-        hipLaunchKernelGGL(k_onehot<__bf16>, grid_for(cells), dim3(kBlock), 0, (hipStream_t)stream, boards, cells,
+        hipLaunchKernelGGL(k_onehot<__bf16>, grid_for(cells, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, cells,
                            (__bf16 *)out);
     return launched("k_onehot");
 }
@@ -262,7 +244,7 @@ int r48_egreedy_actions(const float *q, int64_t n, float eps, uint64_t seed, int
         return fail(R48_EINVAL, "q/actions NULL, q not 16-byte aligned, n < 0 or gid0 < 0");
     if (n == 0)
         return R48_OK;
-    hipLaunchKernelGGL(k_egreedy, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, q, n, eps, (uint32_t)seed,
+    hipLaunchKernelGGL(k_egreedy, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, q, n, eps, (uint32_t)seed,
                        (uint32_t)(seed >> 32), gid0, ctr, actions);
     return launched("k_egreedy");
 }
@@ -277,16 +259,16 @@ int r48_td_target(const float *reward, const uint8_t *done, const float *q_next_
         return R48_OK;
     hipStream_t s = (hipStream_t)stream;
     if (q_next_online && log2_reward)
-        hipLaunchKernelGGL((k_td_target<true, true>), grid_for(n), dim3(kBlock), 0, s, reward, done, q_next_target,
+        hipLaunchKernelGGL((k_td_target<true, true>), grid_for(n, kBlock), dim3(kBlock), 0, s, reward, done, q_next_target,
                            q_next_online, n, gamma, y);
     else if (q_next_online)
-        hipLaunchKernelGGL((k_td_target<true, false>), grid_for(n), dim3(kBlock), 0, s, reward, done, q_next_target,
+        hipLaunchKernelGGL((k_td_target<true, false>), grid_for(n, kBlock), dim3(kBlock), 0, s, reward, done, q_next_target,
                            q_next_online, n, gamma, y);
     else if (log2_reward)
-        hipLaunchKernelGGL((k_td_target<false, true>), grid_for(n), dim3(kBlock), 0, s, reward, done, q_next_target,
+        hipLaunchKernelGGL((k_td_target<false, true>), grid_for(n, kBlock), dim3(kBlock), 0, s, reward, done, q_next_target,
                            nullptr, n, gamma, y);
     else
-        hipLaunchKernelGGL((k_td_target<false, false>), grid_for(n), dim3(kBlock), 0, s, reward, done, q_next_target,
+        hipLaunchKernelGGL((k_td_target<false, false>), grid_for(n, kBlock), dim3(kBlock), 0, s, reward, done, q_next_target,
                            nullptr, n, gamma, y);
     return launched("k_td_target");
 }
@@ -298,10 +280,10 @@ int r48_struct_conv_weight(const float *w, int32_t co, int32_t ci, int32_t out_d
         return fail(R48_EINVAL, "r48_struct_conv_weight: NULL/misaligned argument, bad dtype or 16 ci % 8 != 0");
     const int64_t threads = (int64_t)16 * co * (16 * ci / 8);
     if (out_dtype == R48_F32)
-        hipLaunchKernelGGL(k_struct_weight<float>, grid_for(threads), dim3(kBlock), 0, (hipStream_t)stream, w, co, ci,
+        hipLaunchKernelGGL(k_struct_weight<float>, grid_for(threads, kBlock), dim3(kBlock), 0, (hipStream_t)stream, w, co, ci,
                            (float *)dense);
     else
-        hipLaunchKernelGGL(k_struct_weight<__bf16>, grid_for(threads), dim3(kBlock), 0, (hipStream_t)stream, w, co,
+        hipLaunchKernelGGL(k_struct_weight<__bf16>, grid_for(threads, kBlock), dim3(kBlock), 0, (hipStream_t)stream, w, co,
                            ci, (__bf16 *)dense);
     return launched("k_struct_weight");
 }
@@ -313,10 +295,10 @@ int r48_struct_conv_weight_grad(const void *gdense, int32_t co, int32_t ci, int3
         return fail(R48_EINVAL, "r48_struct_conv_weight_grad: NULL argument or bad dtype");
     const int64_t threads = (int64_t)9 * co * ci;
     if (in_dtype == R48_F32)
-        hipLaunchKernelGGL(k_struct_weight_grad<float>, grid_for(threads), dim3(kBlock), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(k_struct_weight_grad<float>, grid_for(threads, kBlock), dim3(kBlock), 0, (hipStream_t)stream,
                            (const float *)gdense, co, ci, gw);
     else
-        hipLaunchKernelGGL(k_struct_weight_grad<__bf16>, grid_for(threads), dim3(kBlock), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(k_struct_weight_grad<__bf16>, grid_for(threads, kBlock), dim3(kBlock), 0, (hipStream_t)stream,
                            (const __bf16 *)gdense, co, ci, gw);
     return launched("k_struct_weight_grad");
 }

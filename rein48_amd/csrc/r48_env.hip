@@ -20,7 +20,12 @@
 #include "r48_board.h"
 #include "r48_host.h"
 
+using r48::aligned16;
 using r48::Board;
+using r48::DeviceGuard;
+using r48::fail;
+using r48::grid_for;
+using r48::launched;
 
 namespace {
 
@@ -918,29 +923,6 @@ bool ensure_dynamic_lds(const void *kernel, int bytes, int device)
 
 namespace {
 
-int fail(int code, const std::string &msg)
-{
-    g_last_error = msg;
-    return code;
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        if (prev != dev)
-            ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
 int check_env(const r48_env *env, bool need_boards = true)
 {
     if (!env)
@@ -949,16 +931,6 @@ int check_env(const r48_env *env, bool need_boards = true)
         return fail(R48_EINVAL, "no boards bound (call r48_env_bind_boards)");
     return R48_OK;
 }
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(R48_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-    return R48_OK;
-}
-
-inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
 }  // namespace
 
@@ -1011,7 +983,7 @@ int r48_env_bind_boards(r48_env *env, int8_t *boards)
 {
     if (int s = check_env(env, false))
         return s;
-    if (!boards || (reinterpret_cast<uintptr_t>(boards) & 15u))
+    if (!boards || !aligned16(boards))
         return fail(R48_EINVAL, "boards must be a non-NULL 16-byte aligned device pointer");
     env->boards = boards;
     return R48_OK;
@@ -1046,7 +1018,7 @@ int r48_env_reset(r48_env *env, const uint8_t *mask, void *stream)
     if (int s = check_env(env))
         return s;
     DeviceGuard g(env->device);
-    hipLaunchKernelGGL(k_reset, grid_for(env->n), dim3(kBlock), 0, (hipStream_t)stream, env->boards, env->n,
+    hipLaunchKernelGGL(k_reset, grid_for(env->n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, env->boards, env->n,
                        env->gid0, (uint32_t)env->seed, (uint32_t)(env->seed >> 32), env->reset_ctr, mask);
     env->reset_ctr++;
     return launched("k_reset");
@@ -1059,7 +1031,7 @@ int r48_env_fill_random(r48_env *env, uint32_t max_exp, void *stream)
     if (max_exp < 1 || max_exp > 17)
         return fail(R48_EINVAL, "max_exp must be in 1..17");
     DeviceGuard g(env->device);
-    hipLaunchKernelGGL(k_fill_random, grid_for(env->n), dim3(kBlock), 0, (hipStream_t)stream, env->boards,
+    hipLaunchKernelGGL(k_fill_random, grid_for(env->n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, env->boards,
                        env->n, env->gid0, (uint32_t)env->seed, (uint32_t)(env->seed >> 32), max_exp);
     return launched("k_fill_random");
 }
@@ -1072,7 +1044,7 @@ int r48_env_reset_with_draws(r48_env *env, const uint8_t *mask, const uint8_t *r
     if (!rank || !four)
         return fail(R48_EINVAL, "rank and four are required");
     DeviceGuard g(env->device);
-    hipLaunchKernelGGL(k_reset_draws, grid_for(env->n), dim3(kBlock), 0, (hipStream_t)stream, env->boards,
+    hipLaunchKernelGGL(k_reset_draws, grid_for(env->n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, env->boards,
                        env->n, mask, rank, four);
     return launched("k_reset_draws");
 }
@@ -1164,10 +1136,10 @@ int r48_env_step_with_draws(r48_env *env, const int8_t *actions, const uint8_t *
         return fail(R48_EINVAL, "only R48_MERGE_REWARD is valid with injected draws");
     DeviceGuard g(env->device);
     if (flags & R48_MERGE_REWARD)
-        hipLaunchKernelGGL(k_step_draws<true>, grid_for(env->n), dim3(kBlock), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(k_step_draws<true>, grid_for(env->n, kBlock), dim3(kBlock), 0, (hipStream_t)stream,
                            env->boards, env->n, actions, rank, four, done, changed, reward, env->err);
     else
-        hipLaunchKernelGGL(k_step_draws<false>, grid_for(env->n), dim3(kBlock), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(k_step_draws<false>, grid_for(env->n, kBlock), dim3(kBlock), 0, (hipStream_t)stream,
                            env->boards, env->n, actions, rank, four, done, changed, reward, env->err);
     return launched("k_step_draws");
 }
@@ -1183,10 +1155,10 @@ int r48_env_move(r48_env *env, const int8_t *actions, uint32_t flags, uint8_t *c
         return fail(R48_EINVAL, "only R48_MERGE_REWARD is valid for r48_env_move");
     DeviceGuard g(env->device);
     if (flags & R48_MERGE_REWARD)
-        hipLaunchKernelGGL(k_move<true>, grid_for(env->n), dim3(kBlock), 0, (hipStream_t)stream, env->boards,
+        hipLaunchKernelGGL(k_move<true>, grid_for(env->n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, env->boards,
                            env->n, actions, changed, n_blank, reward, env->err);
     else
-        hipLaunchKernelGGL(k_move<false>, grid_for(env->n), dim3(kBlock), 0, (hipStream_t)stream, env->boards,
+        hipLaunchKernelGGL(k_move<false>, grid_for(env->n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, env->boards,
                            env->n, actions, changed, n_blank, reward, env->err);
     return launched("k_move");
 }
@@ -1199,7 +1171,7 @@ int r48_env_spawn(r48_env *env, const uint8_t *mask, const uint8_t *rank, const 
     if (!rank || !four)
         return fail(R48_EINVAL, "rank and four are required");
     DeviceGuard g(env->device);
-    hipLaunchKernelGGL(k_spawn, grid_for(env->n), dim3(kBlock), 0, (hipStream_t)stream, env->boards, env->n,
+    hipLaunchKernelGGL(k_spawn, grid_for(env->n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, env->boards, env->n,
                        mask, rank, four, done);
     return launched("k_spawn");
 }
@@ -1230,7 +1202,7 @@ int r48_env_score(r48_env *env, int32_t *out, void *stream)
     if (!out)
         return fail(R48_EINVAL, "out is NULL");
     DeviceGuard g(env->device);
-    hipLaunchKernelGGL(k_score, grid_for(env->n), dim3(kBlock), 0, (hipStream_t)stream, env->boards, env->n, out);
+    hipLaunchKernelGGL(k_score, grid_for(env->n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, env->boards, env->n, out);
     return launched("k_score");
 }
 
@@ -1266,7 +1238,7 @@ int r48_values_move(int32_t *boards, const int8_t *actions, int64_t n, uint8_t *
         return fail(R48_EINVAL, "boards/actions NULL or n < 0");
     if (n == 0)
         return R48_OK;
-    hipLaunchKernelGGL(k_values_move, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, boards, actions, n,
+    hipLaunchKernelGGL(k_values_move, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, actions, n,
                        changed, reward);
     return launched("k_values_move");
 }
@@ -1278,7 +1250,7 @@ int r48_values_check(const int32_t *boards, int64_t n, int32_t rows, int32_t col
         return fail(R48_EINVAL, "boards NULL, n < 0 or rows/cols outside 1..4");
     if (n == 0)
         return R48_OK;
-    hipLaunchKernelGGL(k_values_check, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, boards, n, rows, cols,
+    hipLaunchKernelGGL(k_values_check, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, n, rows, cols,
                        filled, over);
     return launched("k_values_check");
 }
@@ -1293,7 +1265,7 @@ int r48_values_move_grid(int32_t *boards, int64_t n, int32_t rows, int32_t cols,
     if (changed && hipMemsetAsync(changed, 0, (size_t)n, (hipStream_t)stream) != hipSuccess)
         return fail(R48_EHIP, "hipMemsetAsync failed");
     const int64_t threads = n * (int64_t)(rows > cols ? rows : cols);
-    hipLaunchKernelGGL(k_values_move_grid, grid_for(threads), dim3(kBlock), 0, (hipStream_t)stream, boards, n, rows,
+    hipLaunchKernelGGL(k_values_move_grid, grid_for(threads, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, n, rows,
                        cols, actions, changed);
     return launched("k_values_move_grid");
 }
@@ -1305,7 +1277,7 @@ int r48_values_check_grid(const int32_t *boards, int64_t n, int32_t rows, int32_
         return fail(R48_EINVAL, "boards NULL, n < 0 or rows/cols outside 1..R48_GRID_MAX");
     if (n == 0)
         return R48_OK;
-    hipLaunchKernelGGL(k_values_check_grid, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, boards, n, rows,
+    hipLaunchKernelGGL(k_values_check_grid, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, n, rows,
                        cols, filled, over);
     return launched("k_values_check_grid");
 }

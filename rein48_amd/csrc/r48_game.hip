@@ -9,10 +9,11 @@
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
+#include "r48_host.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::aligned16;
+using r48::fail;
+using r48::launched;
 
 namespace {
 
@@ -41,12 +42,6 @@ __global__ __launch_bounds__(64) void k_game_step1(u32x4 board, uint32_t action,
     }
 }
 
-int fail(int code, const std::string &msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
 }  // namespace
 
 extern "C" {
@@ -55,7 +50,7 @@ int r48_game_step1(const int8_t *board, int32_t action, uint8_t *out, void *stre
 {
     if (!board || !out || action < 0 || action > 3)
         return fail(R48_EINVAL, "board/out NULL or action outside 0..3");
-    if (reinterpret_cast<uintptr_t>(out) & 15u)
+    if (!aligned16(out))
         return fail(R48_EINVAL, "out must be 16-byte aligned");
     for (int k = 0; k < 16; k++)
         if (board[k] < 0 || board[k] > 30)
@@ -63,10 +58,7 @@ int r48_game_step1(const int8_t *board, int32_t action, uint8_t *out, void *stre
     u32x4 v;
     __builtin_memcpy(&v, board, 16);
     hipLaunchKernelGGL(k_game_step1, dim3(1), dim3(64), 0, (hipStream_t)stream, v, (uint32_t)action, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(R48_EHIP, std::string("k_game_step1: ") + hipGetErrorString(e));
-    return R48_OK;
+    return launched("k_game_step1");
 }
 
 int r48_game_step1_out_bytes(void) { return kStep1Out; }

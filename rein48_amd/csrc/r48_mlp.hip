@@ -30,11 +30,13 @@
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
+#include "r48_host.h"
 #include "r48_mlp_common.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::all_aligned16;
+using r48::fail;
+using r48::grid_for;
+using r48::launched;
 
 namespace {
 
@@ -318,23 +320,6 @@ __global__ __launch_bounds__(kBlock) void k_mlp_rollout(int8_t *__restrict__ boa
     }
 }
 
-
-int fail(int code, const std::string &msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(R48_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-    return R48_OK;
-}
-
-inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
 }  // namespace
 
 extern "C" {
@@ -346,12 +331,12 @@ int r48_mlp_policy_forward(const int8_t *boards, int64_t n, const float *w, int3
 {
     if (!boards || !w || n < 0 || gid0 < 0 || (mode != R48_FEAT_VALUES && mode != R48_FEAT_EXPONENTS))
         return fail(R48_EINVAL, "r48_mlp_policy_forward: NULL argument, n/gid0 < 0 or bad mode");
-    if ((reinterpret_cast<uintptr_t>(boards) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(logits)) & 15u)
+    if (!all_aligned16(boards, w, logits))
         return fail(R48_EINVAL, "r48_mlp_policy_forward: boards, w and logits must be 16-byte aligned");
     if (n == 0)
         return R48_OK;
     auto kern = mode == R48_FEAT_VALUES ? k_mlp_forward<R48_FEAT_VALUES> : k_mlp_forward<R48_FEAT_EXPONENTS>;
-    hipLaunchKernelGGL(kern, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, boards, n, w, logits, value, actions,
+    hipLaunchKernelGGL(kern, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, n, w, logits, value, actions,
                        gid0, (uint32_t)seed, (uint32_t)(seed >> 32), ctr);
     return launched("k_mlp_forward");
 }
@@ -364,8 +349,7 @@ int r48_mlp_rollout(int8_t *boards, int64_t n, int32_t n_steps, const float *w, 
     if (!boards || !w || !traj_boards || !actions || !done || n < 0 || gid0 < 0 || n_steps < 1 ||
         (mode != R48_FEAT_VALUES && mode != R48_FEAT_EXPONENTS) || (flags & ~R48_MERGE_REWARD))
         return fail(R48_EINVAL, "r48_mlp_rollout: NULL argument, n/gid0 < 0, n_steps < 1, bad mode or flags");
-    if ((reinterpret_cast<uintptr_t>(boards) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(traj_boards)) &
-        15u)
+    if (!all_aligned16(boards, w, traj_boards))
         return fail(R48_EINVAL, "r48_mlp_rollout: boards, traj_boards and w must be 16-byte aligned");
     if (n == 0)
         return R48_OK;
@@ -373,7 +357,7 @@ int r48_mlp_rollout(int8_t *boards, int64_t n, int32_t n_steps, const float *w, 
     const uint32_t pk0 = (uint32_t)policy_seed, pk1 = (uint32_t)(policy_seed >> 32);
     const uint32_t ek0 = (uint32_t)env_seed, ek1 = (uint32_t)(env_seed >> 32);
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, boards, n, n_steps, w, traj_boards,
+        hipLaunchKernelGGL(kern, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, n, n_steps, w, traj_boards,
                            actions, done, reward, lengths, values, gid0, pk0, pk1, sample_ctr, ek0, ek1, env_step);
     };
 #define R48_MLP_GO(M) \

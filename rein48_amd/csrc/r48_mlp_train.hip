@@ -9,11 +9,12 @@
 #include <string>
 
 #include "../../include/rein48.h"
+#include "r48_host.h"
 #include "r48_mlp_common.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::all_aligned16;
+using r48::fail;
+using r48::launched;
 
 namespace {
 
@@ -866,20 +867,6 @@ __global__ __launch_bounds__(256) void k_mlp_reduce2(const float4 *__restrict__ 
 
 constexpr int kTrainGroups = 512;    // persistent grid: two workgroups of 4 waves per CU (two waves per SIMD) on 256 CUs
 
-int fail(int code, const std::string &msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(R48_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-    return R48_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -950,8 +937,7 @@ int r48_mlp_train_grad(const int8_t *boards, int64_t rows, int64_t n_boards, con
     if (!boards || !actions || !targets || !wn || !w || !workspace || !grad || rows < 1 || n_boards < 1 ||
         (mode != R48_FEAT_VALUES && mode != R48_FEAT_EXPONENTS) || (cm && !counts))
         return fail(R48_EINVAL, "r48_mlp_train_grad: NULL argument, rows/n_boards < 1, bad mode, or cm without counts");
-    if ((reinterpret_cast<uintptr_t>(boards) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(counts) |
-         reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(grad)) & 15u)
+    if (!all_aligned16(boards, w, counts, workspace, grad))
         return fail(R48_EINVAL, "r48_mlp_train_grad: boards, w, counts, workspace and grad must be 16-byte aligned");
     return mlp_train_launch(boards, rows, n_boards, actions, targets, wn, cm, nullptr, counts, beta, mode, w, workspace,
                             grad, stream);
@@ -964,9 +950,7 @@ int r48_mlp_train_grad_seg(const int8_t *boards, int64_t rows, int64_t n_boards,
     if (!boards || !actions || !targets || !seg || !w || !workspace || !grad || rows < 1 || n_boards < 1 ||
         (mode != R48_FEAT_VALUES && mode != R48_FEAT_EXPONENTS))
         return fail(R48_EINVAL, "r48_mlp_train_grad_seg: NULL argument, rows/n_boards < 1 or bad mode");
-    if ((reinterpret_cast<uintptr_t>(boards) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(seg) |
-         reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(workspace) |
-         reinterpret_cast<uintptr_t>(grad)) & 15u)
+    if (!all_aligned16(boards, w, seg, counts, workspace, grad))
         return fail(R48_EINVAL, "r48_mlp_train_grad_seg: boards, w, seg, counts, workspace and grad must be 16-byte "
                                 "aligned");
     return mlp_train_launch(boards, rows, n_boards, actions, targets, nullptr, nullptr, seg, counts, beta, mode, w,

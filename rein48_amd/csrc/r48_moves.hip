@@ -18,35 +18,17 @@
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
+#include "r48_host.h"
 #include "r48_select.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::aligned16;
+using r48::fail;
+using r48::grid_for;
+using r48::launched;
 
 namespace {
 
 constexpr int kBlock = 256;
-
-inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
-int fail(int code, const char *msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        r48::set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-        return R48_EHIP;
-    }
-    return R48_OK;
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 __global__ __launch_bounds__(kBlock) void k_legal(const int8_t *__restrict__ boards, int64_t n,
                                                   uint8_t *__restrict__ legal)
@@ -140,7 +122,7 @@ int r48_boards_legal(const int8_t *boards, int64_t n, uint8_t *legal, void *stre
         return fail(R48_EINVAL, "r48_boards_legal: boards/legal NULL, boards not 16-byte aligned or n < 0");
     if (n == 0)
         return R48_OK;
-    hipLaunchKernelGGL(k_legal, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, boards, n, legal);
+    hipLaunchKernelGGL(k_legal, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, n, legal);
     return launched("k_legal");
 }
 
@@ -152,10 +134,10 @@ int r48_boards_afterstates(const int8_t *boards, int64_t n, int8_t *after, int32
     if (n == 0)
         return R48_OK;
     if (reward)
-        hipLaunchKernelGGL(k_afterstates<true>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, boards, n, after,
+        hipLaunchKernelGGL(k_afterstates<true>, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, n, after,
                            reward, legal);
     else
-        hipLaunchKernelGGL(k_afterstates<false>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, boards, n, after,
+        hipLaunchKernelGGL(k_afterstates<false>, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, boards, n, after,
                            nullptr, legal);
     return launched("k_afterstates");
 }
@@ -168,7 +150,7 @@ int r48_sample_actions_masked(const float *logits, const int8_t *boards, int64_t
                                 "n/gid0 < 0");
     if (n == 0)
         return R48_OK;
-    hipLaunchKernelGGL(k_sample_m, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, logits, boards, n, gid0,
+    hipLaunchKernelGGL(k_sample_m, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, logits, boards, n, gid0,
                        (uint32_t)seed, (uint32_t)(seed >> 32), ctr, actions, logp, entropy);
     return launched("k_sample_m");
 }
@@ -181,7 +163,7 @@ int r48_egreedy_actions_masked(const float *q, const int8_t *boards, int64_t n, 
                                 "n/gid0 < 0");
     if (n == 0)
         return R48_OK;
-    hipLaunchKernelGGL(k_egreedy_m, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, q, boards, n, eps,
+    hipLaunchKernelGGL(k_egreedy_m, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, q, boards, n, eps,
                        (uint32_t)seed, (uint32_t)(seed >> 32), gid0, ctr, actions);
     return launched("k_egreedy_m");
 }
@@ -198,16 +180,16 @@ int r48_td_target_masked(const float *reward, const uint8_t *done, const float *
         return R48_OK;
     hipStream_t s = (hipStream_t)stream;
     if (q_next_online && log2_reward)
-        hipLaunchKernelGGL((k_td_target_m<true, true>), grid_for(n), dim3(kBlock), 0, s, reward, done, q_next_target,
+        hipLaunchKernelGGL((k_td_target_m<true, true>), grid_for(n, kBlock), dim3(kBlock), 0, s, reward, done, q_next_target,
                            q_next_online, next_boards, n, gamma, y);
     else if (q_next_online)
-        hipLaunchKernelGGL((k_td_target_m<true, false>), grid_for(n), dim3(kBlock), 0, s, reward, done, q_next_target,
+        hipLaunchKernelGGL((k_td_target_m<true, false>), grid_for(n, kBlock), dim3(kBlock), 0, s, reward, done, q_next_target,
                            q_next_online, next_boards, n, gamma, y);
     else if (log2_reward)
-        hipLaunchKernelGGL((k_td_target_m<false, true>), grid_for(n), dim3(kBlock), 0, s, reward, done, q_next_target,
+        hipLaunchKernelGGL((k_td_target_m<false, true>), grid_for(n, kBlock), dim3(kBlock), 0, s, reward, done, q_next_target,
                            nullptr, next_boards, n, gamma, y);
     else
-        hipLaunchKernelGGL((k_td_target_m<false, false>), grid_for(n), dim3(kBlock), 0, s, reward, done,
+        hipLaunchKernelGGL((k_td_target_m<false, false>), grid_for(n, kBlock), dim3(kBlock), 0, s, reward, done,
                            q_next_target, nullptr, next_boards, n, gamma, y);
     return launched("k_td_target_m");
 }

@@ -41,36 +41,19 @@
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
+#include "r48_host.h"
 #include "r48_ntuple.h"
 #include "r48_select.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::aligned;
+using r48::aligned16;
+using r48::fail;
+using r48::grid_for;
+using r48::launched;
 
 namespace {
 
 constexpr int kBlock = 256;
-
-inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
-int fail(int code, const std::string &msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        r48::set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-        return R48_EHIP;
-    }
-    return R48_OK;
-}
-
-bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // Staging (r48_ntuple.h) is a compile-time parameter of every kernel: a trailing parameter pack C
 // that is empty for the unstaged kernel -- its arguments are then exactly what they were -- and one
@@ -1149,15 +1132,10 @@ struct PtrArg {
     bool required;
 };
 
-// What every entry point checks first, in this order: boards and n, the layout (expanded into
-// lay), then the pointers as listed. R48_OK, or R48_EINVAL with the message set.
-int check_args(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
-               r48::NtLayout &lay, std::initializer_list<PtrArg> ptrs)
+// The pointers in the order listed: R48_OK, or R48_EINVAL for the first that is NULL though required
+// or misaligned, named in the message.
+int check_ptrs(const char *fn, std::initializer_list<PtrArg> ptrs)
 {
-    if (!boards || !aligned(boards, 16) || n < 0)
-        return fail(R48_EINVAL, std::string(fn) + ": boards NULL or not 16-byte aligned, or n < 0");
-    if (const char *why = r48::nt_expand(cells, m, L, lay))
-        return fail(R48_EINVAL, std::string(fn) + ": bad layout: " + why);
     for (const PtrArg &a : ptrs) {
         if (!a.p && a.required)
             return fail(R48_EINVAL, std::string(fn) + ": " + a.name + " is NULL");
@@ -1165,6 +1143,18 @@ int check_args(const char *fn, const int8_t *boards, int64_t n, const uint8_t *c
             return fail(R48_EINVAL, std::string(fn) + ": " + a.name + " is not " + std::to_string(a.align) + "-byte aligned");
     }
     return R48_OK;
+}
+
+// What every entry point checks first, in this order: boards and n, the layout (expanded into
+// lay), then the pointers as listed. R48_OK, or R48_EINVAL with the message set.
+int check_args(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
+               r48::NtLayout &lay, std::initializer_list<PtrArg> ptrs)
+{
+    if (!boards || !aligned16(boards) || n < 0)
+        return fail(R48_EINVAL, std::string(fn) + ": boards NULL or not 16-byte aligned, or n < 0");
+    if (const char *why = r48::nt_expand(cells, m, L, lay))
+        return fail(R48_EINVAL, std::string(fn) + ": bad layout: " + why);
+    return check_ptrs(fn, ptrs);
 }
 
 // What follows the checks: nothing for n == 0, else f(std::integral_constant<int, L>()) launches
@@ -1236,8 +1226,8 @@ int nt_value(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cel
     if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
         return rc;
     return run("k_nt_value", n, lay.L, [&](auto len) {
-        launch2(st.on, k_nt_value<len()>, k_nt_value<len(), r48::NtCuts>, grid_for(n), kBlock, stream, st.cuts, boards, n,
-                lay, tables, value);
+        launch2(st.on, k_nt_value<len()>, k_nt_value<len(), r48::NtCuts>, grid_for(n, kBlock), kBlock, stream, st.cuts,
+                boards, n, lay, tables, value);
     });
 }
 
@@ -1254,8 +1244,8 @@ int nt_act(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells
     if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
         return rc;
     return run("k_nt_act", n, lay.L, [&](auto len) {
-        launch2(st.on, k_nt_act<len()>, k_nt_act<len(), r48::NtCuts>, grid_for(n), kBlock, stream, st.cuts, boards, n, lay,
-                tables, actions, after, value, reward, legal);
+        launch2(st.on, k_nt_act<len()>, k_nt_act<len(), r48::NtCuts>, grid_for(n, kBlock), kBlock, stream, st.cuts, boards,
+                n, lay, tables, actions, after, value, reward, legal);
     });
 }
 
@@ -1281,9 +1271,9 @@ int nt_td_act(const char *fn, const int8_t *boards, int64_t n, const uint8_t *ce
     if (const int rc = check_cuts(fn, cuts, n_cuts, true, own, st))
         return rc;
     return run("k_nt_td_act", n, lay.L, [&](auto len) {
-        launch2(st.on, k_nt_td_act<len()>, k_nt_td_act<len(), NtCutsOwn>, grid_for(n), kBlock, stream, st.upd, boards, n, lay,
-                tables, prev_after, prev_value, prev_done, prev_valid, actions, after, value, reward, legal, valid_out,
-                delta_out, words(acc), cnt);
+        launch2(st.on, k_nt_td_act<len()>, k_nt_td_act<len(), NtCutsOwn>, grid_for(n, kBlock), kBlock, stream, st.upd,
+                boards, n, lay, tables, prev_after, prev_value, prev_done, prev_valid, actions, after, value, reward, legal,
+                valid_out, delta_out, words(acc), cnt);
     });
 }
 
@@ -1452,8 +1442,8 @@ int nt_accumulate(const char *fn, const int8_t *boards, int64_t n, const float *
     if (const int rc = check_cuts(fn, cuts, n_cuts, true, own, st))
         return rc;
     return run("k_nt_accumulate", n, lay.L, [&](auto len) {
-        launch2(st.on, k_nt_accumulate<len()>, k_nt_accumulate<len(), NtCutsOwn>, grid_for(n), kBlock, stream, st.upd, boards,
-                n, delta, valid, lay, words(acc), cnt);
+        launch2(st.on, k_nt_accumulate<len()>, k_nt_accumulate<len(), NtCutsOwn>, grid_for(n, kBlock), kBlock, stream,
+                st.upd, boards, n, delta, valid, lay, words(acc), cnt);
     });
 }
 
@@ -1469,8 +1459,8 @@ int nt_apply(const char *fn, const int8_t *boards, int64_t n, const uint8_t *val
     if (const int rc = check_cuts(fn, cuts, n_cuts, true, own, st))
         return rc;
     return run("k_nt_apply", n, lay.L, [&](auto len) {
-        launch2(st.on, k_nt_apply<len()>, k_nt_apply<len(), NtCutsOwn>, grid_for(n), kBlock, stream, st.upd, boards, n, valid,
-                lay, step, tables, words(acc), cnt);
+        launch2(st.on, k_nt_apply<len()>, k_nt_apply<len(), NtCutsOwn>, grid_for(n, kBlock), kBlock, stream, st.upd, boards,
+                n, valid, lay, step, tables, words(acc), cnt);
     });
 }
 
@@ -1487,8 +1477,8 @@ int nt_apply_tc(const char *fn, const int8_t *boards, int64_t n, const uint8_t *
     if (const int rc = check_cuts(fn, cuts, n_cuts, true, own, st))
         return rc;
     return run("k_nt_apply_tc", n, lay.L, [&](auto len) {
-        launch2(st.on, k_nt_apply_tc<len()>, k_nt_apply_tc<len(), NtCutsOwn>, grid_for(n), kBlock, stream, st.upd, boards, n,
-                valid, lay, step, tables, tc_e, tc_a, words(acc), cnt);
+        launch2(st.on, k_nt_apply_tc<len()>, k_nt_apply_tc<len(), NtCutsOwn>, grid_for(n, kBlock), kBlock, stream, st.upd,
+                boards, n, valid, lay, step, tables, tc_e, tc_a, words(acc), cnt);
     });
 }
 
@@ -1503,8 +1493,8 @@ int nt_tc_rate(const char *fn, const int8_t *boards, int64_t n, const uint8_t *c
     if (const int rc = check_cuts(fn, cuts, n_cuts, false, nullptr, st))
         return rc;
     return run("k_nt_tc_rate", n, lay.L, [&](auto len) {
-        launch2(st.on, k_nt_tc_rate<len()>, k_nt_tc_rate<len(), r48::NtCuts>, grid_for(n), kBlock, stream, st.cuts, boards, n,
-                lay, tc_e, tc_a, rate_out);
+        launch2(st.on, k_nt_tc_rate<len()>, k_nt_tc_rate<len(), r48::NtCuts>, grid_for(n, kBlock), kBlock, stream, st.cuts,
+                boards, n, lay, tc_e, tc_a, rate_out);
     });
 }
 
@@ -1512,14 +1502,10 @@ int nt_carousel(const char *fn, int8_t *boards, int64_t n, const uint8_t *done, 
                 int8_t *pool, uint8_t *pool_has, uint8_t *seen, uint8_t *turn, uint64_t *starts, uint64_t seed, int64_t gid0,
                 uint32_t ctr, void *stream)
 {
-    for (const PtrArg &a : {PtrArg{"boards", boards, 16, true}, PtrArg{"done", done, 1, true}, PtrArg{"cuts", cuts, 1, true},
-                            PtrArg{"pool", pool, 16, true}, PtrArg{"pool_has", pool_has, 1, true},
-                            PtrArg{"seen", seen, 1, true}, PtrArg{"turn", turn, 1, true}, PtrArg{"starts", starts, 8, false}}) {
-        if (!a.p && a.required)
-            return fail(R48_EINVAL, std::string(fn) + ": " + a.name + " is NULL");
-        if (!aligned(a.p, a.align))
-            return fail(R48_EINVAL, std::string(fn) + ": " + a.name + " is not " + std::to_string(a.align) + "-byte aligned");
-    }
+    if (const int rc = check_ptrs(fn, {{"boards", boards, 16, true}, {"done", done, 1, true}, {"cuts", cuts, 1, true},
+                                       {"pool", pool, 16, true}, {"pool_has", pool_has, 1, true}, {"seen", seen, 1, true},
+                                       {"turn", turn, 1, true}, {"starts", starts, 8, false}}))
+        return rc;
     if (n < 0 || n > 0x7FFFFFFFll)
         return fail(R48_EINVAL, std::string(fn) + ": n = " + std::to_string(n) + " boards, must be 0 .. 2^31 - 1 (the donor is a 32-bit draw)");
     if (const char *why = r48::nt_carousel_cuts_check(cuts, n_cuts))
@@ -1527,12 +1513,13 @@ int nt_carousel(const char *fn, int8_t *boards, int64_t n, const uint8_t *done, 
     if (n == 0)
         return R48_OK;
     const r48::NtCuts c = r48::nt_cuts_pack(cuts, n_cuts);
-    launch(k_nt_carousel_restart, grid_for(n), kBlock, stream, boards, n, done, c, (const int8_t *)pool,
+    launch(k_nt_carousel_restart, grid_for(n, kBlock), kBlock, stream, boards, n, done, c, (const int8_t *)pool,
            (const uint8_t *)pool_has, seen, turn, reinterpret_cast<unsigned long long *>(starts), (uint32_t)seed,
            (uint32_t)(seed >> 32), gid0, ctr);
     if (const int rc = launched("k_nt_carousel_restart"))
         return rc;
-    launch(k_nt_carousel_record, grid_for(n), kBlock, stream, (const int8_t *)boards, n, done, c, pool, pool_has, seen);
+    launch(k_nt_carousel_record, grid_for(n, kBlock), kBlock, stream, (const int8_t *)boards, n, done, c, pool, pool_has,
+           seen);
     return launched("k_nt_carousel_record");
 }
 

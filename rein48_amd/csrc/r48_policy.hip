@@ -30,9 +30,9 @@
 #include "r48_cnn_common.h"
 #include "r48_host.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::all_aligned16;
+using r48::fail;
+using r48::launched;
 
 namespace {
 
@@ -355,12 +355,6 @@ __global__ __launch_bounds__(kThreads, kOccRoll) void k_cnn_rollout(int8_t *__re
     }
 }
 
-int fail(int code, const std::string &msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
 }  // namespace
 
 extern "C" {
@@ -371,9 +365,7 @@ int r48_cnn_policy_forward(const int8_t *boards, int64_t n, const void *wfrag, c
 {
     if (!boards || !wfrag || !bias || n < 0 || gid0 < 0 || (mode != R48_FEAT_VALUES && mode != R48_FEAT_EXPONENTS))
         return fail(R48_EINVAL, "NULL argument, n/gid0 < 0 or bad mode");
-    if ((reinterpret_cast<uintptr_t>(boards) | reinterpret_cast<uintptr_t>(wfrag) |
-         reinterpret_cast<uintptr_t>(boards_out)) & 15u ||
-        (logits && (reinterpret_cast<uintptr_t>(logits) & 15u)))
+    if (!all_aligned16(boards, wfrag, boards_out, logits))
         return fail(R48_EINVAL, "boards, boards_out, wfrag and logits must be 16-byte aligned");
     if (n == 0)
         return R48_OK;
@@ -385,10 +377,7 @@ int r48_cnn_policy_forward(const int8_t *boards, int64_t n, const void *wfrag, c
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, boards, n,
                        (const uint4 *)wfrag, bias, logits, value, actions, boards_out, gid0, (uint32_t)seed,
                        (uint32_t)(seed >> 32), ctr);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(R48_EHIP, std::string("k_cnn_forward: ") + hipGetErrorString(e));
-    return R48_OK;
+    return launched("k_cnn_forward");
 }
 
 int r48_cnn_rollout(int8_t *boards, int64_t n, int32_t n_steps, const void *wfrag, const float *bias, int32_t mode,
@@ -399,8 +388,7 @@ int r48_cnn_rollout(int8_t *boards, int64_t n, int32_t n_steps, const void *wfra
     if (!boards || !wfrag || !bias || !traj_boards || !actions || !done || n < 0 || gid0 < 0 || n_steps < 1 ||
         (mode != R48_FEAT_VALUES && mode != R48_FEAT_EXPONENTS) || (flags & ~R48_MERGE_REWARD))
         return fail(R48_EINVAL, "r48_cnn_rollout: NULL argument, n/gid0 < 0, n_steps < 1, bad mode or flags");
-    if ((reinterpret_cast<uintptr_t>(boards) | reinterpret_cast<uintptr_t>(wfrag) |
-         reinterpret_cast<uintptr_t>(traj_boards)) & 15u)
+    if (!all_aligned16(boards, wfrag, traj_boards))
         return fail(R48_EINVAL, "boards, traj_boards and wfrag must be 16-byte aligned");
     if (n == 0)
         return R48_OK;
@@ -415,10 +403,7 @@ int r48_cnn_rollout(int8_t *boards, int64_t n, int32_t n_steps, const void *wfra
                        (const uint4 *)wfrag, bias, traj_boards, actions, done, reward, lengths, values, gid0, (uint32_t)policy_seed,
                        (uint32_t)(policy_seed >> 32), sample_ctr, (uint32_t)env_seed, (uint32_t)(env_seed >> 32),
                        env_step);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(R48_EHIP, std::string("k_cnn_rollout: ") + hipGetErrorString(e));
-    return R48_OK;
+    return launched("k_cnn_rollout");
 }
 
 }  // extern "C"

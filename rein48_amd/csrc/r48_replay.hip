@@ -26,10 +26,13 @@
 
 #include "../../include/rein48.h"
 #include "r48_board.h"
+#include "r48_host.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::aligned16;
+using r48::DeviceGuard;
+using r48::fail;
+using r48::grid_for;
+using r48::launched;
 
 struct r48_replay {
     int device;
@@ -51,39 +54,6 @@ constexpr uint32_t kRingTag = 0x5A4u;
 constexpr int kMaxWalk = 4096;  // cycle-walk bound (domain <= 4 x size: P(> 4096) ~ 0.75^4096)
 
 enum Src { SRC_GIVEN = 0, SRC_RING = 1, SRC_PERM = 2, SRC_IDENT = 3 };
-
-inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
-int fail(int code, const char *msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        r48::set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-        return R48_EHIP;
-    }
-    return R48_OK;
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev)
-            (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard()
-    {
-        int cur;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev)
-            (void)hipSetDevice(prev);
-    }
-};
 
 __device__ __forceinline__ uint32_t philox_w0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t *w1 = nullptr)
@@ -181,8 +151,6 @@ __global__ __launch_bounds__(kBlock) void k_gather(const int8_t *__restrict__ st
         oidx[i] = ok ? idx : -1;
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 int check_rep(const r48_replay *rep)
 {
     if (!rep || !rep->state)
@@ -210,9 +178,9 @@ int gather(r48_replay *rep, int src, const int64_t *given, int64_t n, int8_t *st
     const uint32_t h = half_bits(rep->size);
     const uint32_t k0 = (uint32_t)rep->seed, k1 = (uint32_t)(rep->seed >> 32);
 #define R48_GATHER(S)                                                                                            \
-    hipLaunchKernelGGL(k_gather<S>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, rep->state, rep->next,   \
-                       rep->action, rep->done, rep->reward, rep->size, n, given, h, rep->sample_ctr, k0, k1, state, \
-                       action, reward, next_state, done, index, rep->err)
+    hipLaunchKernelGGL(k_gather<S>, grid_for(n, kBlock), dim3(kBlock), 0, (hipStream_t)stream, rep->state,      \
+                       rep->next, rep->action, rep->done, rep->reward, rep->size, n, given, h, rep->sample_ctr, \
+                       k0, k1, state, action, reward, next_state, done, index, rep->err)
     switch (src) {
     case SRC_GIVEN: R48_GATHER(SRC_GIVEN); break;
     case SRC_RING: R48_GATHER(SRC_RING); break;
@@ -343,7 +311,7 @@ int r48_replay_store(r48_replay *rep, const int8_t *state, const int8_t *action,
         return R48_OK;
     DeviceGuard g(rep->device);
     const int64_t head = rep->mode == R48_REPLAY_FILL_DRAIN ? rep->size : (rep->head + skip) % rep->cap;
-    hipLaunchKernelGGL(k_store, grid_for(m), dim3(kBlock), 0, (hipStream_t)stream, rep->state, rep->next, rep->action,
+    hipLaunchKernelGGL(k_store, grid_for(m, kBlock), dim3(kBlock), 0, (hipStream_t)stream, rep->state, rep->next, rep->action,
                        rep->done, rep->reward, rep->cap, head, m, state + 16 * skip, action + skip,
                        reward ? reward + skip : nullptr, next_state + 16 * skip, done ? done + skip : nullptr);
     rep->head = (head + m) % rep->cap;

@@ -39,9 +39,10 @@
 #include "r48_board.h"
 #include "r48_host.h"
 
-namespace r48 {
-void set_last_error(const std::string &msg);
-}
+using r48::aligned16;
+using r48::all_aligned16;
+using r48::fail;
+using r48::launched;
 
 namespace {
 
@@ -349,12 +350,6 @@ __global__ __launch_bounds__(256) void k_resnet_pack(const float *const *__restr
     blob[e] = out;
 }
 
-int fail(int code, const char *msg)
-{
-    r48::set_last_error(msg);
-    return code;
-}
-
 }  // namespace
 
 extern "C" {
@@ -364,7 +359,7 @@ int r48_resnet_q_forward(const int8_t *boards, int64_t n, const void *wblob, flo
 {
     if (!boards || !wblob || n < 0 || gid0 < 0 || (!q && !actions))
         return fail(R48_EINVAL, "NULL argument, n/gid0 < 0, or neither q nor actions requested");
-    if (((uintptr_t)wblob & 15u) || ((uintptr_t)boards & 15u) || (q && ((uintptr_t)q & 15u)))
+    if (!all_aligned16(wblob, boards, q))
         return fail(R48_EINVAL, "boards, wblob and q must be 16-byte aligned");
     if (n == 0)
         return R48_OK;
@@ -378,29 +373,19 @@ int r48_resnet_q_forward(const int8_t *boards, int64_t n, const void *wblob, flo
     hipLaunchKernelGGL(k_resnet_q, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, boards, n,
                        reinterpret_cast<const uint4 *>(wblob), q, actions, eps, (uint32_t)seed,
                        (uint32_t)(seed >> 32), gid0, ctr);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        r48::set_last_error(std::string("k_resnet_q: ") + hipGetErrorString(e));
-        return R48_EHIP;
-    }
-    return R48_OK;
+    return launched("k_resnet_q");
 }
 
 int64_t r48_resnet_q_blob_bytes(void) { return (int64_t)kBlobFrags * 1024; }
 
 int r48_resnet_pack(const float *const *ptrs, float bn_eps, void *wblob, void *stream)
 {
-    if (!ptrs || !wblob || ((uintptr_t)wblob & 15u))
+    if (!ptrs || !wblob || !aligned16(wblob))
         return fail(R48_EINVAL, "r48_resnet_pack: NULL or misaligned argument");
     const int64_t total = (int64_t)kBlobFrags * 512;
     hipLaunchKernelGGL(k_resnet_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ptrs,
                        bn_eps, (uint16_t *)wblob);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        r48::set_last_error(std::string("k_resnet_pack: ") + hipGetErrorString(e));
-        return R48_EHIP;
-    }
-    return R48_OK;
+    return launched("k_resnet_pack");
 }
 
 }  // extern "C"
