@@ -4,7 +4,8 @@ the CPU: a wrong reference must not be able to agree with a wrong kernel in test
 Huber against torch's smooth_l1_loss and autograd, Adam against torch.optim.Adam, the returns slab
 against the reference's own executed outputs (tests/golden/a3c_golden.json), the vectorised Philox
 against the C oracle's, the BatchNorm forward and backward (test_bn_kernels_gpu.py's references) against
-torch's batch_norm and autograd. RMSProp and the TD target are oracle/a3c_ref.py's and oracle/dqn_ref.py's,
+torch's batch_norm and autograd, the 3x3 conv and its two gradients (test_conv_kernels_gpu.py's
+references) against torch's conv2d and autograd. RMSProp and the TD target are oracle/a3c_ref.py's and oracle/dqn_ref.py's,
 which test_a3c.py and test_dqn.py cover.
 """
 import json
@@ -204,3 +205,58 @@ def test_bf16_half_ulp_bounds_round_to_nearest():
     assert (err <= hu).all() and err[0] == 2.0 ** -8 and err[0] > 2.0 ** -9 * float(x[0])
     assert (hu >= 2.0 ** -9 * x.numpy() * (1 - 1e-15)).all() and (hu <= 2.0 ** -8 * x.numpy()).all()
     assert U.bf16_half_ulp(0.0) == 0.0
+
+
+@pytest.mark.parametrize("cin", [32, 64])
+@pytest.mark.parametrize("as_torch", [False, True])
+def test_conv_references_match_conv2d_and_autograd(cin, as_torch):
+    """update_refs.conv3x3, conv3x3_dgrad and conv3x3_wgrad at B = 3 against torch.nn.functional.conv2d
+    (padding 1) and autograd in float64, on numpy arrays and on torch tensors (the form the GPU tests
+    evaluate on the device): 1e-13 of the entry's sum of magnitudes (the same few hundred products in
+    another order), and the magnitude sums against the same functions of the absolute values. An
+    input that is zero but for one cell / one tap pins the cell and tap indexing on its own."""
+    B = 3
+    rng = np.random.default_rng(cin)
+    x, dy, add = rng.normal(size=(B, 16, cin)), rng.normal(size=(B, 16, 64)), rng.normal(size=(B, 16, 64))
+    addx = rng.normal(size=(B, 16, cin))
+    w, bias = rng.normal(size=(64, cin, 3, 3)) * 0.1, rng.normal(size=64)
+    wrap = torch.from_numpy if as_torch else (lambda a: a)
+    back = (lambda a: a.numpy()) if as_torch else (lambda a: a)
+
+    def nchw(a):
+        return torch.from_numpy(a).permute(0, 2, 1).reshape(a.shape[0], a.shape[2], 4, 4)
+
+    def cells(t):
+        return t.reshape(t.shape[0], t.shape[1], 16).permute(0, 2, 1).detach().numpy()
+
+    def close(got, want, mag):
+        assert got.shape == want.shape and (np.abs(got - want) <= 1e-13 * mag).all()
+    tx, tw = nchw(x).clone().requires_grad_(True), torch.from_numpy(w).clone().requires_grad_(True)
+    ty = torch.nn.functional.conv2d(tx, tw, torch.from_numpy(bias), padding=1)
+    ty.backward(nchw(dy))
+    for b, a in ((bias, add), (None, None), (bias, None)):
+        y, mag = (back(v) for v in U.conv3x3(wrap(x), wrap(w), None if b is None else wrap(b), None if a is None else wrap(a)))
+        want = cells(ty) + (0.0 if a is None else a) - (0.0 if b is not None else bias)
+        close(y, want, mag)
+        m2 = back(U.conv3x3(wrap(np.abs(x)), wrap(np.abs(w)), None if b is None else wrap(np.abs(b)),
+                            None if a is None else wrap(np.abs(a)))[0])
+        close(mag, m2, m2)
+        assert (mag >= np.abs(y)).all()
+    dx, mag = (back(v) for v in U.conv3x3_dgrad(wrap(dy), wrap(w), wrap(addx)))
+    close(dx, cells(tx.grad) + addx, mag)
+    dx0, mag0 = (back(v) for v in U.conv3x3_dgrad(wrap(dy), wrap(w)))
+    close(dx0, cells(tx.grad), mag0)
+    close(mag, back(U.conv3x3_dgrad(wrap(np.abs(dy)), wrap(np.abs(w)), wrap(np.abs(addx)))[0]), mag)
+    dw, mag = (back(v) for v in U.conv3x3_wgrad(wrap(dy), wrap(x)))
+    close(dw, tw.grad.numpy(), mag)
+    close(mag, back(U.conv3x3_wgrad(wrap(np.abs(dy)), wrap(np.abs(x)))[0]), mag)
+    # one non-zero input entry, one non-zero weight: y is that product at the one cell the tap reaches
+    for cell, kr, kc in ((0, 0, 0), (3, 1, 2), (5, 2, 0), (15, 2, 2), (12, 0, 1)):
+        x1, w1 = np.zeros((1, 16, cin)), np.zeros((64, cin, 3, 3))
+        x1[0, cell, cin - 1], w1[7, cin - 1, kr, kc] = 2.0, 3.0
+        y1 = back(U.conv3x3(wrap(x1), wrap(w1))[0])
+        r, c = cell // 4 - (kr - 1), cell % 4 - (kc - 1)          # the output cell whose tap (kr, kc) reads `cell`
+        want = np.zeros((1, 16, 64))
+        if 0 <= r < 4 and 0 <= c < 4:
+            want[0, 4 * r + c, 7] = 6.0
+        np.testing.assert_array_equal(y1, want)

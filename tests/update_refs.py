@@ -11,6 +11,8 @@ test_update_kernels_host.py (which checks these references on the CPU) and test_
   bn_forward      training-mode BatchNorm (+ residual, ReLU): statistics, coefficients, output, running
                   statistics (bn_from_sums: the same from given sums), with the bounds' magnitude sums
   bn_backward     its backward from the masked gradient (bn_backward_from_sums: from given sums)
+  conv3x3         the 3x3 (pad 1) convolution on the 4x4 grid, channels-last, its data gradient
+                  (conv3x3_dgrad) and weight gradient (conv3x3_wgrad), with the bounds' magnitude sums
 RMSProp and the TD target are oracle/a3c_ref.py's and oracle/dqn_ref.py's.
 """
 import numpy as np
@@ -154,3 +156,73 @@ def bn_backward(g, x, mean, invstd, gamma):
     out.update(dx=out["a"] * (g - out["dbeta"] / n - xc * (invstd * out["dgamma"] / n)),
                g_mag=np.abs(g).sum(0), gx_mag=(np.abs(g) * np.abs(xc)).sum(0))
     return out
+
+
+def _zeros(like, shape):
+    """Float64 zeros of `shape` of the kind of `like`: a numpy array, or a torch tensor on its device."""
+    return like.new_zeros(shape) if hasattr(like, "new_zeros") else np.zeros(shape)
+
+
+def shift_cells(x, dr, dc):
+    """x [B, 16, C] (cell = 4 r + c) -> x at cell (r + dr, c + dc) of the same board, 0 outside the grid."""
+    B, _, C = x.shape
+    g = x.reshape(B, 4, 4, C)
+    out = _zeros(x, (B, 4, 4, C))
+    r0, r1, c0, c1 = max(0, -dr), min(4, 4 - dr), max(0, -dc), min(4, 4 - dc)
+    out[:, r0:r1, c0:c1] = g[:, r0 + dr:r1 + dr, c0 + dc:c1 + dc]
+    return out.reshape(B, 16, C)
+
+
+def conv3x3(x, w, bias=None, add=None):
+    """y[b, p, co] = bias[co] + sum over the taps (kr, kc) and ci of w[co, ci, kr, kc] x[b, p + 4 (kr - 1)
+    + (kc - 1), ci] for the taps that stay on the 4x4 grid (pad 1) (+ add[b, p, co]). x [B, 16, cin],
+    w [cout, cin, 3, 3], bias [cout], add [B, 16, cout], float64: numpy arrays, or torch tensors (on any
+    device: the GPU tests evaluate this same function there). -> (y, mag) [B, 16, cout], mag the sum
+    of the magnitudes of every term of y (the products, the bias, the add)."""
+    B, _, cin = x.shape
+    cout = w.shape[0]
+    y, mag = _zeros(x, (B * 16, cout)), _zeros(x, (B * 16, cout))
+    for t in range(9):
+        xs = shift_cells(x, t // 3 - 1, t % 3 - 1).reshape(B * 16, cin)
+        wt = w[:, :, t // 3, t % 3]
+        y = y + xs @ wt.T
+        mag = mag + abs(xs) @ abs(wt).T
+    if bias is not None:
+        y, mag = y + bias, mag + abs(bias)
+    y, mag = y.reshape(B, 16, cout), mag.reshape(B, 16, cout)
+    if add is not None:
+        y, mag = y + add, mag + abs(add)
+    return y, mag
+
+
+def conv3x3_dgrad(dy, w, add=None):
+    """The gradient of conv3x3 with respect to x: dx[b, q, ci] = sum over the taps and co of
+    w[co, ci, kr, kc] dy[b, q - 4 (kr - 1) - (kc - 1), co] for the output cells on the grid (+ add
+    [b, q, ci]). dy [B, 16, cout] -> (dx, mag) [B, 16, cin]."""
+    B, _, cout = dy.shape
+    cin = w.shape[1]
+    dx, mag = _zeros(dy, (B * 16, cin)), _zeros(dy, (B * 16, cin))
+    for t in range(9):
+        ds = shift_cells(dy, 1 - t // 3, 1 - t % 3).reshape(B * 16, cout)
+        wt = w[:, :, t // 3, t % 3]
+        dx = dx + ds @ wt
+        mag = mag + abs(ds) @ abs(wt)
+    dx, mag = dx.reshape(B, 16, cin), mag.reshape(B, 16, cin)
+    if add is not None:
+        dx, mag = dx + add, mag + abs(add)
+    return dx, mag
+
+
+def conv3x3_wgrad(dy, x):
+    """The gradient of conv3x3 with respect to w: dw[co, ci, kr, kc] = sum over boards and the cells p
+    whose tap stays on the grid of dy[b, p, co] x[b, p + 4 (kr - 1) + (kc - 1), ci]. -> (dw, mag)
+    [cout, cin, 3, 3]."""
+    B, _, cin = x.shape
+    cout = dy.shape[2]
+    d = dy.reshape(B * 16, cout)
+    dw, mag = _zeros(x, (cout, cin, 3, 3)), _zeros(x, (cout, cin, 3, 3))
+    for t in range(9):
+        xs = shift_cells(x, t // 3 - 1, t % 3 - 1).reshape(B * 16, cin)
+        dw[:, :, t // 3, t % 3] = d.T @ xs
+        mag[:, :, t // 3, t % 3] = abs(d).T @ abs(xs)
+    return dw, mag
