@@ -868,6 +868,30 @@ int r48_ntuple_carousel(int8_t *boards, int64_t n, const uint8_t *done, const ui
                         int8_t *pool, uint8_t *pool_has, uint8_t *seen, uint8_t *turn,
                         uint64_t *starts /* nullable */, uint64_t seed, int64_t gid0, uint32_t ctr, void *stream);
 
+/* ---- Replicas: R independent unstaged nets trained in the same launches. A batch of n boards
+ * holds `replicas` replicas (1..64), n a multiple of replicas, per = n / replicas, and board i
+ * belongs to replica r = i / per. tables, acc, cnt, tc_e and tc_a are [replicas][m][16^L]; hit
+ * p = 8t + g of board i uses entry r * (m << 4L) + (t << 4L) + index. steps is float[replicas] IN
+ * DEVICE MEMORY: board i's entries move by steps[r]. Everything else is r48_ntuple_td_act,
+ * r48_ntuple_apply and r48_ntuple_apply_tc word for word, so a call leaves in replica r's slices of
+ * every array the bits those entry points leave when called on that replica's boards, tables and
+ * scratch alone; they do not depend on `replicas` or on the other replicas. The training step is
+ * td_act_replicas, apply[_tc]_replicas(prev_after, ..., prev_valid), the env step, as it is for
+ * one net. R48_EINVAL (before any HIP call) for everything the parents refuse, replicas outside
+ * 1..64, n not a multiple of replicas, steps NULL or not 4-byte aligned, and replicas * m * 16^L
+ * above 2^32 entries (an entry is a uint32). n == 0 is a no-op after these checks. */
+int r48_ntuple_td_act_replicas(const int8_t *boards, int64_t n, int32_t replicas, const uint8_t *cells, int32_t m,
+                               int32_t L, const float *tables, const int8_t *prev_after, const float *prev_value,
+                               const uint8_t *prev_done, const uint8_t *prev_valid, int8_t *actions, int8_t *after,
+                               float *value, int32_t *reward, uint8_t *legal, uint8_t *valid_out, float *delta_out,
+                               int64_t *acc, uint32_t *cnt, void *stream);
+int r48_ntuple_apply_replicas(const int8_t *boards, int64_t n, int32_t replicas, const uint8_t *valid,
+                              const uint8_t *cells, int32_t m, int32_t L, const float *steps, float *tables,
+                              int64_t *acc, uint32_t *cnt, void *stream);
+int r48_ntuple_apply_tc_replicas(const int8_t *boards, int64_t n, int32_t replicas, const uint8_t *valid,
+                                 const uint8_t *cells, int32_t m, int32_t L, const float *steps, float *tables,
+                                 float *tc_e, float *tc_a, int64_t *acc, uint32_t *cnt, void *stream);
+
 /* Thread-local message of the last failed call on this thread ("" if none). */
 const char *r48_last_error(void);
 /* "rein48 <version> gfx950" */

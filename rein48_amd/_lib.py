@@ -164,6 +164,11 @@ SIGNATURES = {
     "r48_ntuple_tc_rate_staged": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
     # boards, n, done, cuts, n_cuts, pool, pool_has, seen, turn, starts, seed, gid0, ctr, stream
     "r48_ntuple_carousel": (C.c_int, [_P, _I64, _P, _P, _I32, _P, _P, _P, _P, _P, _U64, _I64, _U32, _P]),
+    # the replica twins: replicas right after n; apply's step is a device pointer (float[replicas])
+    "r48_ntuple_td_act_replicas": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                             _P, _P, _P, _P]),
+    "r48_ntuple_apply_replicas": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "r48_ntuple_apply_tc_replicas": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "r48_last_error": (C.c_char_p, []),
     "r48_version": (C.c_char_p, []),
 }

@@ -95,6 +95,23 @@
 // nt_staged_update_pull restates the update on the host in the PULL form: an unowned entry is not
 // stored at all, a read resolves to the nearest lower owned stage and a first touch copies it.
 //
+// Replicas (R independent unstaged nets trained in the same launches: k_nt_td_act_rep,
+// k_nt_apply_rep, k_nt_apply_tc_rep). A batch of n boards holds `replicas` replicas, 1..64; n is a
+// multiple of replicas, per = n / replicas >= 1, and board i belongs to replica r = i / per -- by its
+// position in the batch, not by its contents. tables, acc, cnt and with TC tc_e / tc_a are
+// [replicas][m][16^L]. Hit p = 8t + g of board i uses entry
+//     r * (m << 4L) + (t << 4L) + index(b, placed[p]),
+// and replicas * m * 16^L must not exceed 2^32 (an entry is a uint32_t; the entry points refuse more).
+// apply's step is per replica: steps is float[replicas] in device memory and board i moves its
+// entries by steps[r]. Everything else is the unstaged contract word for word: the summation order,
+// nt_td_delta, the fixed-point integer atomics, the owner lane that takes an entry's count by
+// exchange, nt_mean, nt_tc_update. Two replicas share no entry, so a call on [replicas * per] boards
+// leaves in replica r's slices of every array the bits that the unstaged entry point leaves when it
+// is called on that replica's boards, tables and scratch alone, whatever `replicas` is and whatever
+// the other replicas hold. No stages: a replica is an unstaged net. The policy is NtOffset, the
+// lane's offset r * (m << 4L): a wave may straddle a replica boundary (per need not be a multiple of
+// 64), so r, the offset and the step are per-lane values.
+//
 // Carousel shaping (Jaskowski 2016; k_nt_carousel_restart + k_nt_carousel_record, nt_carousel_host
 // on the host). Episodes start in turn from stage 0, 1, ..., S - 1, from a board with which a recent
 // episode ENTERED that stage, so every stage gets an equal share of the episode starts. The carousel
@@ -285,6 +302,33 @@ template <int L>
 R48_HD uint32_t nt_base(const NtCuts &c, int32_t m, const Board &b)
 {
     return (nt_stage(c, b) * (uint32_t)m) << (4 * L);
+}
+
+// ---- replicas ----------------------------------------------------------------------------------
+static constexpr int kNtMaxReplicas = 64;
+
+// the third policy: the offset of the lane's replica in the contiguous [replicas][m][16^L] arrays,
+// r * (m << 4L), whatever the board holds
+struct NtOffset {
+    uint32_t base;
+};
+
+template <int L>
+R48_HD uint32_t nt_base(const NtOffset &o, int32_t, const Board &)
+{
+    return o.base;
+}
+
+// NULL, or what is wrong with the replicas of a batch of n boards of an (m, L) layout
+inline const char *nt_replicas_check(int64_t n, int32_t replicas, int m, int L)
+{
+    if (replicas < 1 || replicas > kNtMaxReplicas)
+        return "replicas must be 1..64";
+    if (n % replicas != 0)
+        return "n is not a multiple of replicas";
+    if ((int64_t)replicas * m * nt_table_size(L) > ((int64_t)1 << 32))
+        return "replicas * m * 16^L exceeds 2^32 entries";
+    return nullptr;
 }
 
 // ---- carousel shaping --------------------------------------------------------------------------

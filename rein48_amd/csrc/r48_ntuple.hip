@@ -4,10 +4,10 @@
 //
 // Every body is stated once, as a __forceinline__ device routine, and the kernels are those
 // routines behind a board load and their stores:
-//   nt_act_board     the one-ply search of a board in one lane   k_nt_act, k_nt_td_act
-//   nt_add_hits      cnt[e] += 1, acc[e] += delta over 8m hits   k_nt_accumulate, k_nt_td_act
-//   nt_owned_hits    the exchange walk that finds an entry's     k_nt_apply (plain mean step),
-//                    one owner lane                              k_nt_apply_tc (TC rule)
+//   nt_act_board     the one-ply search of a board in one lane   k_nt_act, k_nt_td_act, k_nt_td_act_rep
+//   nt_add_hits      cnt[e] += 1, acc[e] += delta over 8m hits   k_nt_accumulate, k_nt_td_act, k_nt_td_act_rep
+//   nt_owned_hits    the exchange walk that finds an entry's     k_nt_apply, k_nt_apply_rep (plain mean step),
+//                    one owner lane                              k_nt_apply_tc, k_nt_apply_tc_rep (TC rule)
 //   nt_wave_q2       the depth-2 search of a board by a wave     k_nt_search<L, 2>, k_nt_search3,
 //                                                                k_nt_search_ruled, nt_wave_q3
 //   nt_wave_q1       the depth-1 search in the same lane mapping k_nt_search<L, 1>, k_nt_search_ruled
@@ -338,6 +338,97 @@ __global__ __launch_bounds__(kBlock) void k_nt_tc_rate(const int8_t *__restrict_
         return;
     const r48::Board b = r48::load_board(boards, i);
     rate_out[i] = r48::nt_tc_rate_mean<L>(r48::nt_pack(b), lay, tc_e, tc_a, r48::nt_base<L>(nt_stg(cuts...), lay.m, b));
+}
+
+// ---- replicas: R independent unstaged nets in the same launches (r48_ntuple.h) -------------------
+// One board per lane like the parents, whose bodies run unchanged under the policy NtOffset: lane i
+// belongs to replica r = i / per and reads and updates entries at the offset r * size, size =
+// m << 4L. per need not be a multiple of 64, so r is a per-lane value; the division is 32-bit
+// wherever the batch allows it (the branch is uniform) and hides behind the table gathers.
+__device__ __forceinline__ uint32_t nt_replica(int64_t i, int64_t n, int64_t per)
+{
+    return n <= 0xFFFFFFFFll ? (uint32_t)i / (uint32_t)per : (uint32_t)(i / per);
+}
+
+// k_nt_td_act with the lane's replica offset: search and accumulate both stay inside replica r.
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_td_act_rep(
+    const int8_t *__restrict__ boards, int64_t n, int64_t per, uint32_t size, const r48::NtLayout lay,
+    const float *__restrict__ tables, const int8_t *__restrict__ prev_after, const float *__restrict__ prev_value,
+    const uint8_t *__restrict__ prev_done, const uint8_t *__restrict__ prev_valid, int8_t *__restrict__ actions,
+    int8_t *__restrict__ after, float *__restrict__ value, int32_t *__restrict__ reward, uint8_t *__restrict__ legal,
+    uint8_t *__restrict__ valid_out, float *__restrict__ delta_out, unsigned long long *__restrict__ acc,
+    uint32_t *__restrict__ cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    const r48::NtOffset off{nt_replica(i, n, per) * size};
+    const r48::Board b = r48::load_board(boards, i);
+    const r48::Board pb = r48::load_board(prev_after, i);
+    const float pv = prev_value[i];
+    const uint32_t pd = prev_done[i], pok = prev_valid[i];
+    const NtMove mv = nt_act_board<L>(b, lay, tables, off);
+    actions[i] = (int8_t)mv.action;
+    *reinterpret_cast<uint4 *>(after + 16 * i) = make_uint4(mv.after.w0, mv.after.w1, mv.after.w2, mv.after.w3);
+    value[i] = mv.value;
+    if (reward)
+        reward[i] = (int32_t)mv.reward;
+    legal[i] = (uint8_t)mv.legal;
+    valid_out[i] = mv.legal != 0u ? 1 : 0;
+    const float delta = r48::nt_td_delta(pd, mv.reward, mv.value, pv);
+    if (delta_out)
+        delta_out[i] = delta;
+    if (pok)
+        nt_add_hits<L>(r48::nt_pack(pb), lay, delta, acc, cnt, r48::nt_base<L>(off, lay.m, pb));
+}
+
+// k_nt_apply per replica: the lane loads its replica's step (steps is float[replicas] in device
+// memory, L2-resident) and owns entries of its own replica only.
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_apply_rep(const int8_t *__restrict__ boards, int64_t n, int64_t per,
+                                                         uint32_t size, const uint8_t *__restrict__ valid,
+                                                         const r48::NtLayout lay, const float *__restrict__ steps,
+                                                         float *__restrict__ tables, unsigned long long *__restrict__ acc,
+                                                         uint32_t *__restrict__ cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || (valid && !valid[i]))
+        return;
+    const uint32_t r = nt_replica(i, n, per);
+    const float step = steps[r];
+    const r48::Board b = r48::load_board(boards, i);
+    nt_owned_hits<L>(
+        r48::nt_pack(b), lay, cnt,
+        [&](uint32_t e, uint32_t c) { tables[e] += step * r48::nt_mean(nt_take_sum(acc, e), c); },
+        r48::nt_base<L>(r48::NtOffset{r * size}, lay.m, b));
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_nt_apply_tc_rep(const int8_t *__restrict__ boards, int64_t n, int64_t per,
+                                                            uint32_t size, const uint8_t *__restrict__ valid,
+                                                            const r48::NtLayout lay, const float *__restrict__ steps,
+                                                            float *__restrict__ tables, float *__restrict__ tc_e,
+                                                            float *__restrict__ tc_a,
+                                                            unsigned long long *__restrict__ acc,
+                                                            uint32_t *__restrict__ cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || (valid && !valid[i]))
+        return;
+    const uint32_t r = nt_replica(i, n, per);
+    const float step = steps[r];
+    const r48::Board b = r48::load_board(boards, i);
+    nt_owned_hits<L>(
+        r48::nt_pack(b), lay, cnt,
+        [&](uint32_t e, uint32_t c) {
+            float w = tables[e], se = tc_e[e], sa = tc_a[e];
+            r48::nt_tc_update(w, se, sa, r48::nt_mean(nt_take_sum(acc, e), c), step);
+            tables[e] = w;
+            tc_e[e] = se;
+            tc_a[e] = sa;
+        },
+        r48::nt_base<L>(r48::NtOffset{r * size}, lay.m, b));
 }
 
 // The expectimax search of r48_ntuple.h, one board per wave: lane = 16 a + c is (move a, cell c).
@@ -1482,6 +1573,71 @@ int nt_apply_tc(const char *fn, const int8_t *boards, int64_t n, const uint8_t *
     });
 }
 
+// ---- the replica entry points: what the parents check, then the replicas (r48_ntuple.h) ---------
+
+// What every replica entry point checks after check_args: replicas, n and the entry count.
+int check_replicas(const char *fn, int64_t n, int32_t replicas, const r48::NtLayout &lay)
+{
+    if (const char *why = r48::nt_replicas_check(n, replicas, lay.m, lay.L))
+        return fail(R48_EINVAL, std::string(fn) + ": bad replicas (" + std::to_string(replicas) + " for n = " +
+                                    std::to_string(n) + "): " + why);
+    return R48_OK;
+}
+
+// entries of one replica, m << 4L (at most 2^27)
+uint32_t replica_size(const r48::NtLayout &lay) { return (uint32_t)lay.m << (4 * lay.L); }
+
+int nt_td_act_replicas(const char *fn, const int8_t *boards, int64_t n, int32_t replicas, const uint8_t *cells, int32_t m,
+                       int32_t L, const float *tables, const int8_t *prev_after, const float *prev_value,
+                       const uint8_t *prev_done, const uint8_t *prev_valid, int8_t *actions, int8_t *after, float *value,
+                       int32_t *reward, uint8_t *legal, uint8_t *valid_out, float *delta_out, int64_t *acc, uint32_t *cnt,
+                       void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay,
+                                  {{"tables", tables, 4, true}, {"prev_after", prev_after, 16, true},
+                                   {"prev_value", prev_value, 4, true}, {"prev_done", prev_done, 1, true},
+                                   {"prev_valid", prev_valid, 1, true}, {"actions", actions, 1, true},
+                                   {"after", after, 16, true}, {"value", value, 4, true}, {"reward", reward, 4, false},
+                                   {"legal", legal, 1, true}, {"valid_out", valid_out, 1, true},
+                                   {"delta_out", delta_out, 4, false}, {"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
+        return rc;
+    if (after == prev_after || value == prev_value || valid_out == prev_valid)
+        return fail(R48_EINVAL, std::string(fn) + ": after, value and valid_out must not be the prev_ buffers (apply "
+                                                  "reads the previous afterstates and flags after this call; swap the buffers then)");
+    if (const int rc = check_replicas(fn, n, replicas, lay))
+        return rc;
+    return run("k_nt_td_act_rep", n, lay.L, [&](auto len) {
+        launch(k_nt_td_act_rep<len()>, grid_for(n, kBlock), kBlock, stream, boards, n, n / replicas, replica_size(lay), lay,
+               tables, prev_after, prev_value, prev_done, prev_valid, actions, after, value, reward, legal, valid_out,
+               delta_out, words(acc), cnt);
+    });
+}
+
+int nt_apply_replicas(const char *fn, const int8_t *boards, int64_t n, int32_t replicas, const uint8_t *valid,
+                      const uint8_t *cells, int32_t m, int32_t L, const float *steps, float *tables, float *tc_e,
+                      float *tc_a, bool tc, int64_t *acc, uint32_t *cnt, void *stream)
+{
+    r48::NtLayout lay;
+    if (const int rc = check_args(fn, boards, n, cells, m, L, lay, {{"steps", steps, 4, true}, {"tables", tables, 4, true}}))
+        return rc;
+    if (tc)
+        if (const int rc = check_ptrs(fn, {{"tc_e", tc_e, 4, true}, {"tc_a", tc_a, 4, true}}))
+            return rc;
+    if (const int rc = check_ptrs(fn, {{"acc", acc, 8, true}, {"cnt", cnt, 4, true}}))
+        return rc;
+    if (const int rc = check_replicas(fn, n, replicas, lay))
+        return rc;
+    return run(tc ? "k_nt_apply_tc_rep" : "k_nt_apply_rep", n, lay.L, [&](auto len) {
+        if (tc)
+            launch(k_nt_apply_tc_rep<len()>, grid_for(n, kBlock), kBlock, stream, boards, n, n / replicas, replica_size(lay),
+                   valid, lay, steps, tables, tc_e, tc_a, words(acc), cnt);
+        else
+            launch(k_nt_apply_rep<len()>, grid_for(n, kBlock), kBlock, stream, boards, n, n / replicas, replica_size(lay),
+                   valid, lay, steps, tables, words(acc), cnt);
+    });
+}
+
 int nt_tc_rate(const char *fn, const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L,
                const uint8_t *cuts, int32_t n_cuts, const float *tc_e, const float *tc_a, float *rate_out, void *stream)
 {
@@ -1690,6 +1846,33 @@ int r48_ntuple_apply_tc_staged(const int8_t *boards, int64_t n, const uint8_t *v
 {
     return nt_apply_tc("r48_ntuple_apply_tc_staged", boards, n, valid, cells, m, L, cuts, n_cuts, step, tables, tc_e, tc_a,
                        acc, cnt, own, stream);
+}
+
+int r48_ntuple_td_act_replicas(const int8_t *boards, int64_t n, int32_t replicas, const uint8_t *cells, int32_t m,
+                               int32_t L, const float *tables, const int8_t *prev_after, const float *prev_value,
+                               const uint8_t *prev_done, const uint8_t *prev_valid, int8_t *actions, int8_t *after,
+                               float *value, int32_t *reward, uint8_t *legal, uint8_t *valid_out, float *delta_out,
+                               int64_t *acc, uint32_t *cnt, void *stream)
+{
+    return nt_td_act_replicas("r48_ntuple_td_act_replicas", boards, n, replicas, cells, m, L, tables, prev_after, prev_value,
+                              prev_done, prev_valid, actions, after, value, reward, legal, valid_out, delta_out, acc, cnt,
+                              stream);
+}
+
+int r48_ntuple_apply_replicas(const int8_t *boards, int64_t n, int32_t replicas, const uint8_t *valid, const uint8_t *cells,
+                              int32_t m, int32_t L, const float *steps, float *tables, int64_t *acc, uint32_t *cnt,
+                              void *stream)
+{
+    return nt_apply_replicas("r48_ntuple_apply_replicas", boards, n, replicas, valid, cells, m, L, steps, tables, nullptr,
+                             nullptr, false, acc, cnt, stream);
+}
+
+int r48_ntuple_apply_tc_replicas(const int8_t *boards, int64_t n, int32_t replicas, const uint8_t *valid,
+                                 const uint8_t *cells, int32_t m, int32_t L, const float *steps, float *tables, float *tc_e,
+                                 float *tc_a, int64_t *acc, uint32_t *cnt, void *stream)
+{
+    return nt_apply_replicas("r48_ntuple_apply_tc_replicas", boards, n, replicas, valid, cells, m, L, steps, tables, tc_e,
+                             tc_a, true, acc, cnt, stream);
 }
 
 int r48_ntuple_tc_rate(const int8_t *boards, int64_t n, const uint8_t *cells, int32_t m, int32_t L, const float *tc_e,

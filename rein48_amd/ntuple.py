@@ -30,6 +30,10 @@ NTupleConfig.carousel=(c_1, ..., c_k) (cuts of the same form) turns on carousel 
 (Jaskowski 2016): episodes start in turn from every stage, from a remembered board with which a
 recent episode entered it, so the late stages get as many episode starts as the first
 (NTupleTrainer; the contract is in rein48_amd/csrc/r48_ntuple.h). Opt-in; carousel=() is off.
+
+NTupleReplicaTrainer trains up to 64 independent unstaged nets -- seeds, or an alpha sweep -- in the
+same three launches per step: each replica has its own tables, boards and alpha, and is bit for bit
+the solo fused trainer on its boards (the contract is in r48_ntuple.h, "Replicas").
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -149,6 +153,34 @@ class NTupleNet:
             self.own = torch.zeros(shape, dtype=torch.uint8, device=self.device)
             self.own[0] = 1
         self._lib = _lib.load()
+
+    @classmethod
+    def _over(cls, layout, tables, acc, cnt, tc_e=None, tc_a=None):
+        """An unstaged net over given tensors, each contiguous [m, 16^L] on one GPU (tc_e and tc_a
+        both or neither): nothing is allocated, every method works on the caller's storage
+        (NTupleReplicaTrainer.net)."""
+        self = cls.__new__(cls)
+        self.cells = layout_cells(layout)
+        self.m, self.L = len(self.cells), len(self.cells[0])
+        shape = (self.m, 16 ** self.L)
+        for t, name, dtype in ((tables, "tables", torch.float32), (acc, "acc", torch.int64), (cnt, "cnt", torch.int32),
+                               (tc_e, "tc_e", torch.float32), (tc_a, "tc_a", torch.float32)):
+            if t is None and name in ("tc_e", "tc_a"):
+                continue
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != tables.device:
+                raise ValueError("%s must be a contiguous %s tensor %r on %s" % (name, dtype, shape, tables.device))
+        if (tc_e is None) != (tc_a is None):
+            raise ValueError("tc_e and tc_a come together")
+        self.device = tables.device
+        if self.device.type != "cuda":
+            raise ValueError("NTupleNet device must be a GPU, got %s" % self.device)
+        flat = [c for t in self.cells for c in t]
+        self._cells = (C.c_uint8 * len(flat))(*flat)
+        self.cuts, self.S, self._cuts, self.own = (), 1, (C.c_uint8 * 0)(), None
+        self.tables, self.acc, self.cnt = tables, acc, cnt
+        self.tc, self.tc_e, self.tc_a = tc_e is not None, tc_e, tc_a
+        self._lib = _lib.load()
+        return self
 
     def _fn(self, name):
         """The entry point `name`, or its _staged twin on a staged net."""
@@ -586,3 +618,133 @@ class NTupleTrainer:
 
     def policy(self, depth=1, rule=None):
         return self.net.policy(depth, rule)
+
+
+MAX_REPLICAS = 64
+
+
+def replica_steps(replicas, alphas, alpha, m):
+    """The per-replica steps of NTupleReplicaTrainer as a list of `replicas` Python floats, each a
+    float32 value: alpha_r / (8m) rounded as c_float(alpha / (8.0 * m)) rounds the solo trainer's
+    step. `replicas` is 1..64; `alphas` is None (`alpha` everywhere) or `replicas` finite numbers.
+    Needs no GPU."""
+    if isinstance(replicas, bool) or int(replicas) != replicas:
+        raise ValueError("replicas is a whole number, got %r" % (replicas,))
+    replicas = int(replicas)
+    if not 1 <= replicas <= MAX_REPLICAS:
+        raise ValueError("replicas is 1..%d, got %d" % (MAX_REPLICAS, replicas))
+    m = int(m)
+    if not 1 <= m <= 8:
+        raise ValueError("a layout has 1..8 tuples, got %d" % m)
+    if alphas is None:
+        alphas = (alpha,) * replicas
+    alphas = tuple(float(a) for a in alphas)
+    if len(alphas) != replicas:
+        raise ValueError("alphas holds one alpha per replica (%d), got %d" % (replicas, len(alphas)))
+    if any(a != a or a in (float("inf"), float("-inf")) for a in alphas):
+        raise ValueError("alphas are finite numbers, got %r" % (alphas,))
+    return [C.c_float(a / (8.0 * m)).value for a in alphas]
+
+
+class NTupleReplicaTrainer:
+    """`replicas` independent unstaged n-tuple nets trained in the same three launches per step
+    (the contract is in rein48_amd/csrc/r48_ntuple.h, "Replicas"): cfg.n_boards boards PER REPLICA
+    in one VecGame of replicas * cfg.n_boards boards with seed cfg.seed, replica r playing the
+    global board ids r * n_boards .. -- its own games, which is its independent "seed" -- on its own
+    tables [replicas, m, 16^L] and, with `alphas`, its own alpha (None: cfg.alpha everywhere).
+    train_step() is NTupleTrainer's fused step: td_act_replicas, apply_replicas (cfg.tc:
+    apply_tc_replicas), env.step with auto-reset, the "previous" buffers swapped by reference. Replica
+    r's slices hold the bits a solo NTupleTrainer(fused=True) with alpha_r on VecGame(n_boards,
+    seed, board_offset=r * n_boards) holds after the same number of steps. cfg.fused is not
+    consulted; cfg.stages and cfg.carousel are refused (replicas of staged nets are not built, and
+    the carousel's donor draw ranges over the whole batch and would mix replicas). net(r) is replica
+    r as an NTupleNet over views. Single GPU."""
+
+    def __init__(self, cfg: NTupleConfig, replicas, alphas=None, device="cuda:0"):
+        if tuple(cfg.stages):
+            raise ValueError("NTupleReplicaTrainer: replicas of staged nets are not built (cfg.stages = %r)" % (cfg.stages,))
+        if tuple(cfg.carousel):
+            raise ValueError("NTupleReplicaTrainer: the carousel is not built for replicas (cfg.carousel = %r)"
+                             % (cfg.carousel,))
+        self.cfg = cfg
+        self.cells = layout_cells(cfg.layout)
+        self.m, self.L = len(self.cells), len(self.cells[0])
+        self.step_values = replica_steps(replicas, alphas, cfg.alpha, self.m)
+        self.replicas = R = len(self.step_values)
+        if R * self.m * 16 ** self.L > 1 << 32:
+            raise ValueError("%d replicas of %d tables of 16^%d entries exceed 2^32 entries" % (R, self.m, self.L))
+        self.per = int(cfg.n_boards)
+        if self.per < 1:
+            raise ValueError("n_boards is at least 1 board per replica, got %d" % self.per)
+        n = R * self.per
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("NTupleReplicaTrainer device must be a GPU, got %s" % self.device)
+        self.rank = 0
+        self.tc = bool(cfg.tc)
+        self.env = VecGame(n, device=self.device, seed=cfg.seed)
+        self.device = d = self.env.device
+        self.env.reset()
+        flat = [c for t in self.cells for c in t]
+        self._cells = (C.c_uint8 * len(flat))(*flat)
+        shape = (R, self.m, 16 ** self.L)
+        self.tables = torch.zeros(shape, dtype=torch.float32, device=d)
+        self.acc = torch.zeros(shape, dtype=torch.int64, device=d)
+        self.cnt = torch.zeros(shape, dtype=torch.int32, device=d)
+        self.tc_e = torch.zeros(shape, dtype=torch.float32, device=d) if self.tc else None
+        self.tc_a = torch.zeros(shape, dtype=torch.float32, device=d) if self.tc else None
+        self.steps = torch.tensor(self.step_values, dtype=torch.float32, device=d)   # exact: the values are float32's
+        self.actions = torch.zeros(n, dtype=torch.int8, device=d)
+        self.reward = torch.zeros(n, dtype=torch.int32, device=d)
+        self.legal = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.after, self.prev_after = (torch.zeros((n, 16), dtype=torch.int8, device=d) for _ in range(2))
+        self.value, self.prev_value = (torch.zeros(n, dtype=torch.float32, device=d) for _ in range(2))
+        self.prev_done = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.valid, self.prev_valid = (torch.zeros(n, dtype=torch.uint8, device=d) for _ in range(2))
+        self.delta = torch.zeros(n, dtype=torch.float32, device=d)
+        self.updates = 0
+        self._lib = _lib.load()
+
+    def net(self, r):
+        """Replica r as an NTupleNet whose tables, acc, cnt, tc_e and tc_a are views of the trainer's:
+        nothing is allocated. value, act, the searches, play_episodes, save and state_dict work on it
+        as on any unstaged net, and a solo NTupleNet.load reads what it saved."""
+        r = int(r)
+        if not 0 <= r < self.replicas:
+            raise ValueError("replica %d of %d" % (r, self.replicas))
+        return NTupleNet._over(self.cells, self.tables[r], self.acc[r], self.cnt[r],
+                               self.tc_e[r] if self.tc else None, self.tc_a[r] if self.tc else None)
+
+    def replica(self, t, r):
+        """Replica r's rows of a per-board tensor of the trainer (env.boards, prev_after, ...)."""
+        return t[r * self.per:(r + 1) * self.per]
+
+    @torch.no_grad()
+    def train_step(self):
+        env, lib = self.env, self._lib
+        n, s = env.n, _stream(env.boards)
+        lay = (self._cells, self.m, self.L)
+        check(lib.r48_ntuple_td_act_replicas(
+            ptr(env.boards), n, self.replicas, *lay, ptr(self.tables), ptr(self.prev_after), ptr(self.prev_value),
+            ptr(self.prev_done), ptr(self.prev_valid), ptr(self.actions), ptr(self.after), ptr(self.value),
+            ptr(self.reward), ptr(self.legal), ptr(self.valid), ptr(self.delta), ptr(self.acc), ptr(self.cnt), s))
+        if self.tc:
+            check(lib.r48_ntuple_apply_tc_replicas(ptr(self.prev_after), n, self.replicas, ptr(self.prev_valid), *lay,
+                                                   ptr(self.steps), ptr(self.tables), ptr(self.tc_e), ptr(self.tc_a),
+                                                   ptr(self.acc), ptr(self.cnt), s))
+        else:
+            check(lib.r48_ntuple_apply_replicas(ptr(self.prev_after), n, self.replicas, ptr(self.prev_valid), *lay,
+                                                ptr(self.steps), ptr(self.tables), ptr(self.acc), ptr(self.cnt), s))
+        env.step(self.actions, auto_reset=True, done_out=self.prev_done)
+        self.valid, self.prev_valid = self.prev_valid, self.valid
+        self.after, self.prev_after = self.prev_after, self.after
+        self.value, self.prev_value = self.prev_value, self.value
+        self.updates += 1
+
+    def train_steps(self, k):
+        """k train_step()s in one Python call."""
+        for _ in range(int(k)):
+            self.train_step()
+
+    def policy(self, r, depth=1, rule=None):
+        return self.net(r).policy(depth, rule)
